@@ -13,7 +13,7 @@ N > 1, one rank per GPU over RCCL: either an external launcher starts the ranks 
 or plain `python bench.py --gpus N` starts them itself through the same torch.distributed.run command line
 (`plan_launch`); a box with fewer than N GPUs is an error, not a smaller run.  Frames are independent, so
 ranks shard the batch with no data-path collective ("weak": per-GPU work fixed).  Rank 0
-prints ONE JSON line with the whole-job rate, the roofline of the dominant kernel
+prints ONE JSON line with the whole-job rate; with `--full` also the roofline of the dominant kernel
 (k_decode, timed with HIP events on its stream) and the CPU baseline (the oracle's
 restatement of the reference loops, timed on this box's host cores, rank 0 at N=1 only).
 
@@ -39,6 +39,14 @@ reported under "loss_paths" (never as `value`): `holes` (one lost packet per fra
 pass), `stray10` (10 % of the frames compacted after a drop / shuffled: fix-up pass), `general` (every frame compacted
 into 127 slots with per-frame packet counts: the general mapping for every frame).
 `--workload`, `--outputs`, `--exchange`, `--pcie` select other configurations / ablations.
+
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: the setup above (tuner, placement), the W
+warm-up steps, the K timed steps and the line (metric, value, unit, higher_is_better, dtype, ms_per_step, config, placement,
+tuner).  `--full` adds everything else this docstring names, as before: the roofline (HIP events in the timed region, the box's
+copy rate, the committed PMC traffic), the oracle self-check, loss paths, other workloads, latency, standalone kernels, the
+drop-in API rows and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step left in the output buffers
+(dump_outputs: float32 / float64 .npy files, a fixed seeded sample of the large arrays, 64 MB at most) so that two builds can be
+compared output for output; the inputs are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -809,6 +817,48 @@ def _report_row(fn, *a, **kw):
         return {"error": f"{type(e).__name__}: {e}"[:300], "where": traceback.format_exc().strip().splitlines()[-3:]}
 
 
+def dump_outputs(out, dirname, budget=64 << 20, whole_max=4 << 20, seed=0x5EED):
+    """--dump-outputs: what the timed path handed its caller, as DIR/<name>.npy (':' of a name becomes '_').  Integers of up to
+    16 bits and float32 go out as float32, wider integers and float64 as float64 (exact either way).  An array whose converted
+    size is at most `whole_max` is written whole; a larger one as a fixed sample of its points (rows of the flattened array, a
+    trailing axis of 3 kept together), drawn with `seed` from the number of points alone -- so every plane and cloud of the
+    same size is sampled at the same pixels, in ascending order, and two runs with the same arguments sample alike.  The
+    sample size halves until the whole dump fits in `budget` bytes."""
+    import torch
+
+    def rows_of(t):
+        c = 3 if t.dim() >= 2 and t.shape[-1] == 3 else 1
+        return t.numel() // c, c
+
+    def out_itemsize(t):
+        return 4 if (t.dtype == torch.float32 or (not t.is_floating_point() and t.element_size() <= 2)) else 8
+
+    def plan(k):
+        return sum(t.numel() * out_itemsize(t) if t.numel() * out_itemsize(t) <= whole_max
+                   else min(k, rows_of(t)[0]) * rows_of(t)[1] * out_itemsize(t) for t in out.values())
+
+    k = 1 << 18
+    while k > 1 and plan(k) > budget:
+        k //= 2
+    os.makedirs(dirname, exist_ok=True)
+    for name in sorted(out):
+        t = out[name]
+        isz = out_itemsize(t)
+        if not t.is_floating_point() and t.element_size() >= 4:   # no unsigned 32 / 64-bit gathers in torch: move the bits
+            t = t.view(torch.int32 if t.element_size() == 4 else torch.int64)
+        if t.numel() * isz > whole_max:
+            n, c = rows_of(t)
+            idx = np.sort(np.random.default_rng([seed, n]).choice(n, size=min(k, n), replace=False))
+            t = t.reshape(n, c).index_select(0, torch.from_numpy(idx).to(t.device))
+            if c == 1:
+                t = t.reshape(-1)
+        a = t.cpu().numpy()
+        src = out[name].dtype
+        if src in (torch.uint32, torch.uint64):
+            a = a.view(np.uint32 if src == torch.uint32 else np.uint64)
+        np.save(os.path.join(dirname, name.replace(":", "_") + ".npy"), a.astype(np.float32 if isz == 4 else np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -853,7 +903,15 @@ def main():
                     help="also time host->GPU packets + decode + GPU->host XYZ (reported separately)")
     ap.add_argument("--exchange", action="store_true",
                     help="also time RCCL scatter of packets / gather of XYZ (reported separately)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take everything beside the headline: roofline, oracle self-check, loss paths, other workloads, "
+                         "latency, standalone kernels, drop-in API and the CPU baseline (off: setup, warm-up, timed steps, line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's frames when N > 1) to DIR/<name>.npy (float32 / float64; "
+                         "a fixed, seeded sample of each large array, 64 MB at most in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     if not torch.cuda.is_available():
@@ -896,8 +954,9 @@ def main():
     # measured behind the placement search -- tens of device-to-device clones and tens of GB allocated and freed by this process --
     # the child's copy stream from the device ran at 27.8 GB/s instead of 50.7 (round 6; the headline and every resident row are
     # unaffected either way)
+    full = args.full
     drop_in_early = None
-    if rank == 0 and world == 1 and args.workload == "dual" and args.outputs == "full" and not args.no_extras:
+    if full and rank == 0 and world == 1 and args.workload == "dual" and args.outputs == "full" and not args.no_extras:
         drop_in_early = _report_row(time_drop_in)
 
     profile, bits, chan, dst_names, xyz_names, _, _, wl_label = WORKLOADS[args.workload]
@@ -995,7 +1054,8 @@ def main():
     # --rotate-inputs R > 1 (a diagnostic, not the metric): R copies of the packet batch are decoded in turn, so that
     # no step finds its input in the 256 MB Infinity Cache left there by the step before
     inputs = [packets] + [packets.clone() for _ in range(max(0, args.rotate_inputs - 1))]
-    hp.ctx.timing(args.time_every)   # HIP events around every N-th decode kernel of the timed region (each pair costs the stream 2 - 3 us)
+    if full:   # the roofline's kernel time: HIP events around every N-th decode kernel of the timed region (each pair costs the stream 2 - 3 us)
+        hp.ctx.timing(args.time_every)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -1013,20 +1073,23 @@ def main():
              "note": "measured: this process timed the candidates during setup (24 calls before the warm-up); cache: read from "
                      "OUSTER_HIP_TUNING_CACHE / BatchOptions::tuning_cache, nothing timed (tests/test_gpu_tuning_cache.py)"}
     hp.ctx.timing(False)
+    if args.dump_outputs and rank == 0:   # before anything below overwrites or replaces the outputs
+        dump_outputs(out, args.dump_outputs)
 
-
-    # context for the roofline: what a plain device-to-device copy reaches on THIS box right now
-    # (boxes of the pool differ by up to ~35 % in sustained HBM bandwidth)
-    cp_src = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
-    cp_dst = torch.empty_like(cp_src)
-    cp_dst.copy_(cp_src)
-    torch.cuda.synchronize()
-    c0 = time.perf_counter()
-    for _ in range(5):
+    box_copy_gbps = None
+    if full:
+        # context for the roofline: what a plain device-to-device copy reaches on THIS box right now
+        # (boxes of the pool differ by up to ~35 % in sustained HBM bandwidth)
+        cp_src = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+        cp_dst = torch.empty_like(cp_src)
         cp_dst.copy_(cp_src)
-    torch.cuda.synchronize()
-    box_copy_gbps = 5 * 2 * (1 << 30) / (time.perf_counter() - c0) / 1e9
-    del cp_src, cp_dst
+        torch.cuda.synchronize()
+        c0 = time.perf_counter()
+        for _ in range(5):
+            cp_dst.copy_(cp_src)
+        torch.cuda.synchronize()
+        box_copy_gbps = 5 * 2 * (1 << 30) / (time.perf_counter() - c0) / 1e9
+        del cp_src, cp_dst
 
     pcie = None
     if args.pcie:
@@ -1146,7 +1209,7 @@ def main():
 
     # self-check of what the timed steps left in HBM (rank 0, outside the timed region)
     validated, max_dxyz, checked = None, None, None
-    if rank == 0 and args.outputs == "full":     # (--no-cpu skips the CPU baseline leg only)
+    if full and rank == 0 and args.outputs == "full":     # (--no-cpu skips the CPU baseline leg only)
         try:
             validated, max_dxyz, checked = validate_against_oracle(
                 hp, profile, packets, out, shifts, lut_args, len(lut_args), sorted({0, 7 % F, F // 2, F - 1}))
@@ -1154,7 +1217,7 @@ def main():
             validated, max_dxyz, checked = None, None, [f"validation did not run: {type(e).__name__}: {e}"[:200]]
     # what the opt-in placement search (BatchOptions::auto_placement / HotPath.refine_placement) would have
     # given on this box: run AFTER the timed region and the self-check, reported beside the headline, never as `value`
-    if rank == 0 and world == 1 and args.placement == "first" and args.outputs == "full" and not args.no_extras:
+    if full and rank == 0 and world == 1 and args.placement == "first" and args.outputs == "full" and not args.no_extras:
         t_setup = time.perf_counter()
         try:
             out, rep = hp.refine_placement(packets, out, draws=args.placement_draws, ballast_gb=args.placement_ballast_gb)
@@ -1164,11 +1227,11 @@ def main():
     # the paths the metric never touches, on the same output buffers, outside the timed region and
     # after the self-check (they overwrite the outputs)
     loss_paths = None
-    if rank == 0 and not args.no_loss_paths and args.outputs == "full":
+    if full and rank == 0 and not args.no_loss_paths and args.outputs == "full":
         loss_paths = _report_row(time_loss_paths, hp, packets, out, F, algorithmic_bytes_per_frame(args.workload))
     # every other BASELINE config and the small-batch latency view, in the driver-visible line
     other_workloads, latency, latency_python, standalone, drop_in = None, None, None, None, None
-    if rank == 0 and world == 1 and args.workload == "dual" and args.outputs == "full" and not args.no_extras:
+    if full and rank == 0 and world == 1 and args.workload == "dual" and args.outputs == "full" and not args.no_extras:
         other_workloads = _report_row(time_other_workloads, placement="first" if args.placement == "first" else "refine",
                                       scan_tries=args.placement_scan_tries, scan_stride_gb=args.placement_scan_stride_gb)   # same default
         latency_python = _report_row(time_small_batches)
@@ -1181,7 +1244,7 @@ def main():
     # HBM bytes per launch from the committed PMC passes (rocprofv3 cannot wrap a run from inside):
     # only quoted when the committed profile is of exactly this workload and output set.
     traffic, traffic_src = None, None
-    if args.outputs == "full":
+    if full and args.outputs == "full":
         import glob
         cands = []
         for pj in sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)),
@@ -1248,39 +1311,42 @@ def main():
                                             "two draws) and of up to 10 of the packet buffer (HotPath.pick_placement)"
                                             % (args.placement_tries, args.placement_stride_gb))},
             "placement": placement,
-            "roofline": {"bound": "hbm",
-                         "kernel": kernel_name,
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                         "achieved_step": round(step_gbps, 1),
-                         "frac_step": round(step_gbps / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "kernel_ms_avg": round(kern_ms, 4), "launches_timed": n_launch,
-                         "box_d2d_copy_GBps": round(box_copy_gbps, 1)},
-            "validated": validated, "max_abs_dxyz_m": max_dxyz, "validated_frames": checked,
-            "loss_paths": loss_paths,
-            "other_workloads": other_workloads,
-            "latency": latency,
-            "latency_python": latency_python,
-            "standalone": standalone,
-            "drop_in": drop_in,
-            "cpu_baseline": None,
         }
-        if placement and "first_allocation_ms" in placement:   # --placement refine: the first allocation's fraction next to the kept draw's
-            line["roofline"]["first_allocation_ms_per_call"] = placement["first_allocation_ms"]
-            line["roofline"]["first_allocation_frac_step"] = round(
-                bytes_per_launch / (placement["first_allocation_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-        if placement and isinstance(placement.get("scan"), dict) and placement["scan"].get("incumbent_ms"):
-            # ... and what the library's default search alone had reached before the whole sets were drawn (same clock: 8 back-to-back
-            # decodes into the buffers it kept) -- three numbers for one run: first allocation, library default, this setup
-            line["roofline"]["library_default_search_ms_per_call"] = placement["scan"]["incumbent_ms"]
-            line["roofline"]["library_default_search_frac_step"] = round(
-                bytes_per_launch / (placement["scan"]["incumbent_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-        if placement and "search_after_timed_region" in placement:   # default: what the opt-in search would have given
-            rep = placement["search_after_timed_region"]
-            line["roofline"]["searched_placement_ms_per_call"] = rep["kept_ms"]
-            line["roofline"]["searched_placement_frac_step"] = round(bytes_per_launch / (rep["kept_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+        if full:   # everything beside the headline (bench.py --full)
+            line.update({
+                "roofline": {"bound": "hbm",
+                             "kernel": kernel_name,
+                             "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                             "achieved_step": round(step_gbps, 1),
+                             "frac_step": round(step_gbps / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                             "traffic_source": traffic_src,
+                             "algorithmic_bytes_per_launch": bytes_per_launch,
+                             "kernel_ms_avg": round(kern_ms, 4), "launches_timed": n_launch,
+                             "box_d2d_copy_GBps": round(box_copy_gbps, 1)},
+                "validated": validated, "max_abs_dxyz_m": max_dxyz, "validated_frames": checked,
+                "loss_paths": loss_paths,
+                "other_workloads": other_workloads,
+                "latency": latency,
+                "latency_python": latency_python,
+                "standalone": standalone,
+                "drop_in": drop_in,
+                "cpu_baseline": None,
+            })
+            if placement and "first_allocation_ms" in placement:   # --placement refine: the first allocation's fraction next to the kept draw's
+                line["roofline"]["first_allocation_ms_per_call"] = placement["first_allocation_ms"]
+                line["roofline"]["first_allocation_frac_step"] = round(
+                    bytes_per_launch / (placement["first_allocation_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+            if placement and isinstance(placement.get("scan"), dict) and placement["scan"].get("incumbent_ms"):
+                # ... and what the library's default search alone had reached before the whole sets were drawn (same clock: 8 back-to-back
+                # decodes into the buffers it kept) -- three numbers for one run: first allocation, library default, this setup
+                line["roofline"]["library_default_search_ms_per_call"] = placement["scan"]["incumbent_ms"]
+                line["roofline"]["library_default_search_frac_step"] = round(
+                    bytes_per_launch / (placement["scan"]["incumbent_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+            if placement and "search_after_timed_region" in placement:   # default: what the opt-in search would have given
+                rep = placement["search_after_timed_region"]
+                line["roofline"]["searched_placement_ms_per_call"] = rep["kept_ms"]
+                line["roofline"]["searched_placement_frac_step"] = round(bytes_per_launch / (rep["kept_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
         line["tuner"] = tuner
         line["rccl_ranks"] = rccl_ranks
         line["collective_backend"] = coll
@@ -1290,7 +1356,7 @@ def main():
             line["exchange"] = exchange
         if pcie:
             line["pcie_inclusive"] = pcie
-        if world == 1 and not args.no_cpu and args.workload == "dual":
+        if full and world == 1 and not args.no_cpu and args.workload == "dual":
             line["cpu_baseline"] = _report_row(cpu_baseline, pool, shifts)
         print(json.dumps(line), flush=True)
     if world > 1:

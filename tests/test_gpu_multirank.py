@@ -142,7 +142,7 @@ def test_eight_ranks_dry_run_batch512_exchange_on_whatever_is_here():
     one rank per GPU (no fallback); otherwise all eight ranks on cuda:0 over gloo (BENCH_ONE_DEVICE=1: same code, the exchange
     tensors travel through host memory).  The 512 frames scattered from rank 0, decoded by eight ranks and gathered back must
     leave the clouds ONE rank leaves; the line carries every rank's own timing and kernel."""
-    base = ["--steps", "2", "--warmup", "1", "--workload", "batch512", "--no-cpu", "--exchange", "--no-loss-paths", "--no-extras"]
+    base = ["--steps", "2", "--warmup", "1", "--workload", "batch512", "--full", "--no-cpu", "--exchange", "--no-loss-paths", "--no-extras"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BENCH_ONE_DEVICE", "BENCH_BACKEND")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     one = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--placement", "first"] + base, capture_output=True, text=True,

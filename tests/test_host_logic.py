@@ -72,6 +72,37 @@ def test_bench_workload_definition(oracle):
     assert np.allclose(b2l, cal.beam_to_lidar) and np.allclose(l2s, cal.lidar_to_sensor)
 
 
+def test_bench_dump_outputs_sample(tmp_path):
+    """`bench.py --dump-outputs DIR` (bench.dump_outputs) on host tensors shaped like the benchmark's: exact float32 / float64
+    values, small arrays whole, large ones sampled at the same seeded pixels for every plane and cloud, within the 64 MB budget,
+    and the same files from two dumps of the same outputs."""
+    import torch
+    import bench
+    F, H, W = 16, bench.H, bench.W
+    g = torch.Generator().manual_seed(7)
+    out = {"RANGE": torch.randint(0, 1 << 18, (F, H, W), generator=g).to(torch.uint32),
+           "REFLECTIVITY": torch.randint(0, 256, (F, H, W), generator=g).to(torch.uint8),
+           "destaggered:RANGE": torch.randint(0, 1 << 18, (F, H, W), generator=g).to(torch.uint32),
+           "xyz:RANGE": torch.randn((F, H * W, 3), generator=g),
+           "timestamp": (torch.arange(F * W).reshape(F, W) + (1 << 40)).to(torch.uint64),
+           "frame_meta": torch.randint(0, 256, (F, 24), generator=g).to(torch.uint8)}
+    bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == sorted(n.replace(":", "_") for n in out)
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    for name, a in got.items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, np.load(tmp_path / "b" / (name + ".npy"))), name
+    assert got["RANGE"].dtype == np.float64 and got["REFLECTIVITY"].dtype == np.float32 and got["xyz_RANGE"].dtype == np.float32
+    assert np.array_equal(got["timestamp"], out["timestamp"].numpy().astype(np.float64))       # 128 KB: whole
+    assert np.array_equal(got["frame_meta"], out["frame_meta"].numpy().astype(np.float32))
+    n = F * H * W
+    idx = np.sort(np.random.default_rng([0x5EED, n]).choice(n, size=1 << 18, replace=False))
+    assert np.array_equal(got["RANGE"], out["RANGE"].numpy().reshape(-1)[idx].astype(np.float64))
+    assert np.array_equal(got["REFLECTIVITY"], out["REFLECTIVITY"].numpy().reshape(-1)[idx].astype(np.float32))
+    assert np.array_equal(got["xyz_RANGE"], out["xyz:RANGE"].numpy().reshape(-1, 3)[idx])
+
+
 def test_bench_gpus_flag_plans_the_launch():
     """`bench.py --gpus N`: one rank per GPU either way -- under a launcher WORLD_SIZE must equal N, without one the
     script starts N ranks itself through torch.distributed.run on 127.0.0.1."""

@@ -122,7 +122,7 @@ from ouster_sdk_amd.device import HotPath
 N = 256
 prof, bits, chan, dst, xyz = bench.WORKLOADS[wl][:5]
 H, W = bench.H, bench.W
-sys.argv = ["bench.py", "--workload", wl, "--steps", "20", "--warmup", "3", "--no-cpu"]
+sys.argv = ["bench.py", "--workload", wl, "--steps", "20", "--warmup", "3", "--full", "--no-cpu"]
 import io, contextlib
 cap = io.StringIO()
 with contextlib.redirect_stdout(cap):

@@ -4,7 +4,8 @@
 reference's fixtures.  The host half (zlib inflate on a parked crew of up to 128 threads, straight into one pinned buffer)
 dominates either way."""
 import sys, time, json, os
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import test_gpu_osf as T
 from oracle import osf_oracle as Z

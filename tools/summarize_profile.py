@@ -15,7 +15,7 @@ def rows(path):
 
 
 print(f"# rocprofv3 summary ({os.path.basename(d)})\n")
-print(f"Command: `python bench.py --workload {workload} --steps 20 --warmup 3 --no-cpu` (kernel trace); PMC passes use "
+print(f"Command: `python bench.py --workload {workload} --steps 20 --warmup 3 --full --no-cpu` (kernel trace); PMC passes use "
       "`--steps 3 --warmup 1`.\n")
 print("## kernel stats (rocprofv3 --kernel-trace --stats)\n")
 print("| kernel | calls | avg us | min us | max us | % |")
