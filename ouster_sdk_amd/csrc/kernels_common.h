@@ -7,15 +7,7 @@
 
 #include "ouster_hip_dev.h"
 
-// 1: the f32 xyz transpose of the fused kernels goes through ds_bpermute (no LDS scratch);
-// 0: through a 12 KB wave-private LDS scratch (the r01 form, kept for A/B builds)
-#ifndef OUSTER_XYZ_PERMUTE
-#define OUSTER_XYZ_PERMUTE 1
-#endif
-
 namespace ouster_hip_dev {
-
-constexpr size_t XYZ_SCRATCH_BYTES = OUSTER_XYZ_PERMUTE ? 0 : 4 * 192 * 16;
 
 // ------------------------------------------------------------------------------------
 // small helpers
@@ -618,10 +610,7 @@ __device__ __forceinline__ uint32_t block_parsable_dev(uint32_t H, uint32_t cpp)
 
 // hdr_words (optional): the frame's slots' (measurement_id | valid << 16) already packed in global memory.
 // s_hd[count * cpp]: (measurement_id | valid << 16) of every buffer slot, left behind for the caller (the fix-up pass looks
-// up "is slot c live and at home" there).  LDS words needed: resolve_lds_words().
-__host__ __device__ inline size_t resolve_lds_words(uint32_t W, uint32_t npo, uint32_t slots_per_frame, uint32_t cpp) {
-    return (size_t)3 * W + npo + 2 * (size_t)slots_per_frame + (size_t)slots_per_frame * cpp + 4;
-}
+// up "is slot c live and at home" there).  LDS words needed: resolve_lds_words() (decode_plan.h).
 struct ResolveLds {
     int32_t *pix, *hdr, *z, *pkm;
     uint32_t *pkt, *hd;

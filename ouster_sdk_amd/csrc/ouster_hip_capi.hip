@@ -69,34 +69,21 @@ struct DevBuf {
 
 }  // namespace
 
-// experiment / test knobs of a context: defaults from OUSTER_HIP_* environment variables read ONCE in
-// ouster_hip_ctx_create, changed afterwards with ouster_hip_ctx_set_knob (never getenv on the call path)
-struct Knobs {
-    int tile = 0;             // OUSTER_HIP_TILE: force k_decode's tile width (64/32/16)
-    int wide = -1;            // OUSTER_HIP_WIDE: -1 auto (tuner), 0 narrow, 64/128/256/512 force k_decode_wide
-    int wide_kb = 64;         // OUSTER_HIP_WIDE_KB: LDS budget of a wide tile image
-    int wide_rows = 0;        // OUSTER_HIP_WIDE_ROWS: force the rows of a wide tile (experiments)
-    int wide_min_blocks = 512;  // OUSTER_HIP_WIDE_MIN_BLOCKS: smaller launches stay on k_decode
-    int tune = 1;             // OUSTER_HIP_TUNE: 0 pins the default wide variant
-    int xcd = 1;              // OUSTER_HIP_XCD: 0 disables the XCD-aware block -> frame mapping
-    int fast = 1;             // OUSTER_HIP_FAST: 0 sends every frame through the general mapping
-    int dewarp_single_pass = 0;  // OUSTER_HIP_DWF_SINGLE: 1 = k_dwf_single instead of count / scan / emit (slower)
-    int beam_lds = 1;         // OUSTER_HIP_BEAM_LDS: 0 keeps k_decode's per-beam table in global memory (A/B)
-    int fixup = 1;            // tests only: 0 skips the fix-up pass (flagged frames are then left undone)
-    int small = 1;            // OUSTER_HIP_SMALL: small batches: 1 = wide tiles of few rows (optimistic pass + fix-up pass; any other buffer shape: the
-                              //   one-launch k_decode_wide_resolved) | 2 = the one-launch form always | 0 = k_decode's narrow tiles as in r03
-    int fixup_rows = 0;       // OUSTER_HIP_FIXUP_ROWS: rows of a fix-up tile (0: 8)
-    int hdr_words = 1;        // OUSTER_HIP_HDR_WORDS: 0 = the fix-up pass reads the column headers from the packets again (A/B)
-    int fixup_wide = 1;       // OUSTER_HIP_FIXUP_WIDE: 1 = the fix-up pass on wide tiles where the format allows | 0 = 64-column tiles | 64 / 128 / 256 force
-    int stream = -1;          // OUSTER_HIP_STREAM: -1 auto | 0 never | 128 / 256 force k_decode_stream with that tile width when eligible
-    int stream_rows = 0;      // OUSTER_HIP_STREAM_ROWS: force the rows of a streamed tile (experiments)
-    int stream_wait = 1;      // OUSTER_HIP_STREAM_WAIT: 1 vmcnt(0) before a prefetched tile is used | 0 rely on the in-order counter
-    int stream_min_tiles = 8; // OUSTER_HIP_STREAM_MIN_TILES: tiles per workgroup below which a launch stays on k_decode_wide
-    int stream_order = 0;     // OUSTER_HIP_STREAM_ORDER: item order of k_decode_stream's groups (experiments)
-    int slotmap = 1;          // OUSTER_HIP_SLOTMAP: 0 = buffers without one slot per column go through k_decode's general tiles
-                              //   (every tile scans the frame's headers) instead of k_slotmap + k_decode_wide
-    int dwf_stream = -1;      // OUSTER_HIP_DWF_STREAM: the frame dewarp's emit kernel: -1 auto | 0 k_dwf_emit | 1 the persistent k_dwf_emit_stream where eligible
-    int stream_loader = 4;    // OUSTER_HIP_STREAM_LOADER: loader waves of k_decode_stream2 (0 = k_decode_stream: every wave fetches)
+// k_decode variant (64-column tiles / wide tiles of 128 or 256 columns / the persistent kernel) per workload, picked by
+// timing each candidate on the first calls: which one is faster depends on how the output planes happen to be placed
+// in HBM
+struct Tune {
+    int best = -2;  // -2: still measuring; 0: narrow; 128 / 256: wide; 1000 + tile width: the persistent kernel
+    int calls = 0;
+    bool from_cache = false;   // `best` was read from the tuning cache file, not timed by this context
+    static constexpr int ROUNDS = 4, NCAND = 5, SAMPLES = NCAND * ROUNDS;
+    hipEvent_t ev[SAMPLES][2] = {};  // up to five candidates x ROUNDS consecutive launches
+    float ms[NCAND] = {0, 0, 0, 0, 0};  // fastest warm sample of each candidate
+    void destroy() {
+        for (auto& pr : ev)
+            for (hipEvent_t& e : pr)
+                if (e) (void)hipEventDestroy(e), e = nullptr;
+    }
 };
 
 struct ouster_hip_ctx {
@@ -124,24 +111,18 @@ struct ouster_hip_ctx {
     uint32_t timing_every = 1, timing_calls = 0;   // HIP events around every timing_every-th decode kernel (an event record costs the stream 2 - 3 us)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     size_t ev_used = 0;
-    // k_decode variant (64-column tiles / wide tiles of 128 or 256 columns) per workload, picked by
-    // timing each candidate on the first calls: which one is faster depends on how the output
-    // planes happen to be placed in HBM
-    struct Tune {
-        int best = -2;  // -2: still measuring; 0: narrow; 128 / 256: wide; 1000 + tile width: the persistent kernel
-        int calls = 0;
-        bool from_cache = false;   // `best` was read from the tuning cache file, not timed by this context
-        static constexpr int ROUNDS = 4, NCAND = 5, SAMPLES = NCAND * ROUNDS;
-        hipEvent_t ev[SAMPLES][2] = {};  // up to five candidates x ROUNDS consecutive launches
-        float ms[NCAND] = {0, 0, 0, 0, 0};  // fastest warm sample of each candidate
-    };
-    std::map<uint64_t, Tune> tune;
+    std::map<uint64_t, Tune> tune;       // the variant tuner, by workload key (decode_plan.h)
     // verdicts of earlier processes (ouster_hip_ctx_set_tuning_cache): workload key -> chosen variant, for THIS device and library
     std::string tune_cache_path, tune_cache_id;
     std::map<uint64_t, int> tune_cache;
     const char* last_tuner = "none";     // how the last ouster_hip_decode chose its variant
     int last_tile_cols = 0, last_tile_rows = 0;  // tile of the last k_decode launch
 };
+
+static void tune_forget(ouster_hip_ctx* c) {   // the one place the tuner's events are destroyed
+    for (auto& kv : c->tune) kv.second.destroy();
+    c->tune.clear();
+}
 
 struct ouster_hip_format {
     ouster_hip_format_desc desc;
@@ -298,31 +279,9 @@ int ouster_hip_ctx_create(int device, void* stream, ouster_hip_ctx** out) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
             c->resident_wgs = 2u * (uint32_t)cus, c->cus = (uint32_t)cus;
     }
-    {   // the only place the environment is read
-        auto env_int = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
-        Knobs& k = c->knobs;
-        k.tile = env_int("OUSTER_HIP_TILE", k.tile);
-        k.wide = env_int("OUSTER_HIP_WIDE", k.wide);
-        k.wide_kb = env_int("OUSTER_HIP_WIDE_KB", k.wide_kb);
-        k.wide_rows = env_int("OUSTER_HIP_WIDE_ROWS", k.wide_rows);
-        k.wide_min_blocks = env_int("OUSTER_HIP_WIDE_MIN_BLOCKS", k.wide_min_blocks);
-        k.tune = env_int("OUSTER_HIP_TUNE", k.tune);
-        k.xcd = env_int("OUSTER_HIP_XCD", k.xcd);
-        k.fast = env_int("OUSTER_HIP_FAST", k.fast);
-        k.beam_lds = env_int("OUSTER_HIP_BEAM_LDS", k.beam_lds);
-        k.dewarp_single_pass = env_int("OUSTER_HIP_DWF_SINGLE", k.dewarp_single_pass);
-        k.stream = env_int("OUSTER_HIP_STREAM", k.stream);
-        k.stream_rows = env_int("OUSTER_HIP_STREAM_ROWS", k.stream_rows);
-        k.stream_wait = env_int("OUSTER_HIP_STREAM_WAIT", k.stream_wait);
-        k.stream_min_tiles = env_int("OUSTER_HIP_STREAM_MIN_TILES", k.stream_min_tiles);
-        k.stream_order = env_int("OUSTER_HIP_STREAM_ORDER", k.stream_order);
-        k.stream_loader = env_int("OUSTER_HIP_STREAM_LOADER", k.stream_loader);
-        k.dwf_stream = env_int("OUSTER_HIP_DWF_STREAM", k.dwf_stream);
-        k.slotmap = env_int("OUSTER_HIP_SLOTMAP", k.slotmap);
-        k.fixup_wide = env_int("OUSTER_HIP_FIXUP_WIDE", k.fixup_wide);
-        k.small = env_int("OUSTER_HIP_SMALL", k.small);
-        k.hdr_words = env_int("OUSTER_HIP_HDR_WORDS", k.hdr_words);
-        k.fixup_rows = env_int("OUSTER_HIP_FIXUP_ROWS", k.fixup_rows);
+    for (int i = 0; i < knob_count; ++i) {   // the only place the environment is read
+        const KnobDef& k = knob_table[i];
+        if (const char* e = k.env ? getenv(k.env) : nullptr) c->knobs.*k.member = atoi(e);
     }
     if (const char* e = getenv("OUSTER_HIP_TUNING_CACHE")) (void)ouster_hip_ctx_set_tuning_cache(c, e);
     if (stream == OUSTER_HIP_STREAM_NULL) {
@@ -363,10 +322,7 @@ void ouster_hip_ctx_destroy(ouster_hip_ctx* c) {
         (void)hipEventDestroy(p.first);
         (void)hipEventDestroy(p.second);
     }
-    for (auto& kv : c->tune)
-        for (auto& pr : kv.second.ev)
-            for (hipEvent_t e : pr)
-                if (e) (void)hipEventDestroy(e);
+    tune_forget(c);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -377,43 +333,17 @@ int ouster_hip_ctx_device(ouster_hip_ctx* c) { return c ? c->device : -1; }
 
 int ouster_hip_ctx_set_knob(ouster_hip_ctx* c, const char* name, int value) {
     if (!c || !name) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    const std::string n = name;
-    Knobs& k = c->knobs;
-    if (n == "tile") k.tile = value;
-    else if (n == "wide") k.wide = value;
-    else if (n == "wide_kb") k.wide_kb = value;
-    else if (n == "wide_rows") k.wide_rows = value;
-    else if (n == "wide_min_blocks") k.wide_min_blocks = value;
-    else if (n == "tune") k.tune = value;
-    else if (n == "retune") {   // forget what the variant tuner learnt (the caller moved its buffers: pick_placement)
+    if (!strcmp(name, "retune")) {   // forget what the variant tuner learnt (the caller moved its buffers: pick_placement)
         if (value) {
             (void)hipStreamSynchronize(c->stream);
-            for (auto& kv : c->tune)
-                for (auto& pr : kv.second.ev)
-                    for (hipEvent_t e : pr)
-                        if (e) (void)hipEventDestroy(e);
-            c->tune.clear();
+            tune_forget(c);
             c->tune_cache.clear();   // what this context read from the cache file is void as well: it re-measures and appends anew
         }
+        return OUSTER_HIP_OK;
     }
-    else if (n == "xcd") k.xcd = value;
-    else if (n == "fast") k.fast = value;
-    else if (n == "fixup") k.fixup = value;
-    else if (n == "fixup_wide") k.fixup_wide = value;
-    else if (n == "small") k.small = value;
-    else if (n == "hdr_words") k.hdr_words = value;
-    else if (n == "fixup_rows") k.fixup_rows = value;
-    else if (n == "beam_lds") k.beam_lds = value;
-    else if (n == "dewarp_single_pass") k.dewarp_single_pass = value;
-    else if (n == "dwf_stream") k.dwf_stream = value;
-    else if (n == "stream") k.stream = value;
-    else if (n == "stream_rows") k.stream_rows = value;
-    else if (n == "stream_wait") k.stream_wait = value;
-    else if (n == "stream_min_tiles") k.stream_min_tiles = value;
-    else if (n == "stream_order") k.stream_order = value;
-    else if (n == "stream_loader") k.stream_loader = value;
-    else if (n == "slotmap") k.slotmap = value;
-    else return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "unknown knob '%s'", name);
+    const KnobDef* k = find_knob(name);
+    if (!k) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "unknown knob '%s'", name);
+    c->knobs.*k->member = value;
     return OUSTER_HIP_OK;
 }
 
@@ -721,18 +651,75 @@ static bool fast_possible(const Knobs& kn, uint32_t slots_per_frame, const Geome
     return kn.fast && (uint64_t)slots_per_frame * g.columns_per_packet == g.columns_per_frame;
 }
 
-int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const uint8_t* packets,
-                      size_t packet_stride, uint32_t slots_per_frame,
-                      const uint32_t* packet_counts, uint32_t n_frames,
-                      const uint64_t* host_timestamps, const ouster_hip_frame_out* out,
-                      const int32_t* pixel_shift_by_row, const ouster_hip_lut* const* luts,
-                      uint32_t n_luts) {
-    if (!ctx || !fmt || !out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (n_frames == 0) return OUSTER_HIP_OK;
+// ---- the variant tuner ----------------------------------------------------------------------------
+// Four launches of each candidate, back to back (a launch that follows a different variant is not representative of the
+// steady state: alternating the candidates made the 64-column kernel look 8 % faster than it then ran).  Single launches
+// vary by ~10 %, mostly upwards, and the candidates can be within 1-5 % of each other: each candidate's fastest sample
+// counts, its first one (cold code, cold TLB, another variant's write-backs still draining) only when nothing else landed.
+// The clocks are polled, never waited for: until all samples have landed the default variant runs.
+// every sample of `t` is queued: once all have landed, the fastest candidate becomes the verdict (and goes to the cache file)
+static void tune_collect(ouster_hip_ctx* c, uint64_t key, Tune& t, const int* cand, int nc) {
+    constexpr int R = Tune::ROUNDS;
+    const int NS = nc * R;
+    for (int i = 0; i < NS; ++i)
+        if (hipEventQuery(t.ev[i][1]) != hipSuccess) {
+            (void)hipGetLastError();
+            return;
+        }
+    float cold[Tune::NCAND] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < NS; ++i) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, t.ev[i][0], t.ev[i][1]) != hipSuccess || ms <= 0) continue;
+        float& slot = (i % R == 0) ? cold[i / R] : t.ms[i / R];
+        if (slot == 0 || ms < slot) slot = ms;
+    }
+    for (int k = 0; k < nc; ++k)
+        if (t.ms[k] == 0) t.ms[k] = cold[k];
+    t.best = 256;
+    float best_ms = 0;
+    for (int k = 0; k < nc; ++k)
+        if (t.ms[k] > 0 && (best_ms == 0 || t.ms[k] < best_ms)) { t.best = cand[k]; best_ms = t.ms[k]; }
+    tune_cache_append(c, key, t.best, best_ms);
+}
+
+// What this call launches: a verdict (measured, or an earlier process's from the cache file), the next sample of a
+// candidate (then `record` / `slot` say where its two events go), or the default variant while samples are in flight.
+struct TuneStep {
+    int variant;
+    Tune* record;
+    int slot;
+};
+static TuneStep tune_step(ouster_hip_ctx* c, uint64_t key, const int* cand, int nc) {
+    if (c->tune.size() > 64 && !c->tune.count(key)) tune_forget(c);   // bounded: forget everything, re-learn
+    const bool fresh = !c->tune.count(key);
+    Tune& t = c->tune[key];
+    if (fresh) {   // an earlier process (or rank) has timed this workload on this device: launch its choice from call 1
+        auto hit = c->tune_cache.find(key);
+        if (hit != c->tune_cache.end() && std::find(cand, cand + nc, hit->second) != cand + nc) {
+            t.best = hit->second;
+            t.from_cache = true;
+        }
+    }
+    const int NS = nc * Tune::ROUNDS;
+    if (t.best == -2 && t.calls >= NS) tune_collect(c, key, t, cand, nc);
+    if (t.best != -2) {
+        c->last_tuner = t.from_cache ? "cache" : "measured";
+        return {t.best, nullptr, -1};
+    }
+    c->last_tuner = "measuring";
+    if (t.calls >= NS) return {256, nullptr, -1};   // every sample is queued, not all have landed
+    const int slot = t.calls++;
+    return {cand[slot / Tune::ROUNDS], &t, slot};
+}
+
+// ---- decode: the steps of ouster_hip_decode, in its order -----------------------------------------------------------------
+// argument checks; also makes the context's device current
+static int check_decode_call(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const uint8_t* packets, size_t packet_stride,
+                             uint32_t slots_per_frame, const ouster_hip_frame_out* out, const int32_t* pixel_shift_by_row,
+                             const ouster_hip_lut* const* luts, uint32_t n_luts, bool any_dst, bool any_xyz) {
     if (!packets) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "packets is NULL");
     const Geometry& g = fmt->g;
-    const Knobs& kn = ctx->knobs;
-    const uint32_t W = g.columns_per_frame, H = g.pixels_per_column;
+    const uint32_t W = g.columns_per_frame, H = g.pixels_per_column, nf = fmt->desc.n_fields;
     if (packet_stride < g.lidar_packet_size || (packet_stride & 3) || ((uintptr_t)packets & 3))
         return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT,
                     "packet_stride must be >= lidar_packet_size and 4-byte granular");
@@ -743,11 +730,6 @@ int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const u
     if (W > 65536 || W / g.columns_per_packet > 8192)
         return fail(OUSTER_HIP_ERR_UNSUPPORTED, "more than 65536 columns or 8192 packets per frame");
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-
-    const uint32_t nf = fmt->desc.n_fields;
-    bool any_dst = false, any_xyz = (out->xyz[0] || out->xyz[1]);
-    for (uint32_t i = 0; i < nf; ++i) any_dst |= out->destaggered[i] != nullptr;
     if (any_dst && !pixel_shift_by_row)
         return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "image height does not match shifts size");
     if (out->gate_counts) {
@@ -774,21 +756,28 @@ int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const u
                 return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "LUT %u lives on GPU %d, the context on GPU %d", i,
                             luts[i]->device, ctx->device);
     }
+    return OUSTER_HIP_OK;
+}
 
-    // ---- scratch: per-frame state words (all-zero between calls: the fix-up pass cleans up after
-    // itself), destagger offsets, LUT descriptors, packet counts
+// scratch: per-frame state words (all-zero between calls: the fix-up pass cleans up after itself), packet counts,
+// destagger offsets, LUT descriptors.  xyzm: 0 no xyz | 1 / 2 separable tables, f32 / f64 output | 3 full LUT
+static int stage_decode_tables(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, uint32_t slots_per_frame,
+                               const uint32_t* packet_counts, uint32_t n_frames, const ouster_hip_frame_out* out,
+                               const int32_t* pixel_shift_by_row, const ouster_hip_lut* const* luts, uint32_t n_luts,
+                               bool any_dst, bool any_xyz, const uint32_t** d_counts, int* xyzm) {
+    const Geometry& g = fmt->g;
+    const uint32_t W = g.columns_per_frame, H = g.pixels_per_column;
     {
         const void* before = ctx->state.p;
         if (ctx->state.ensure(((size_t)2 * n_frames + FS_WORDS) * 8)) return fail(OUSTER_HIP_ERR_RUNTIME, "hipMalloc(state) failed");
-        if (ctx->state.p != before || ctx->state_dirty) HIP_TRY(hipMemsetAsync(ctx->state.p, 0, ctx->state.cap, st));
-        ctx->state_dirty = fast_possible(kn, slots_per_frame, g);  // until the fix-up pass has been queued
+        if (ctx->state.p != before || ctx->state_dirty) HIP_TRY(hipMemsetAsync(ctx->state.p, 0, ctx->state.cap, ctx->stream));
+        ctx->state_dirty = fast_possible(ctx->knobs, slots_per_frame, g);  // until the fix-up pass has been queued
     }
     if (out->frame_meta && ctx->tile_valid.ensure((size_t)n_frames * ((W + 15) / 16) * 2))
         return fail(OUSTER_HIP_ERR_RUNTIME, "hipMalloc(tile_valid) failed");
-    const uint32_t n_packets_out = W / g.columns_per_packet;
-    const uint32_t* d_counts = nullptr;
+    *d_counts = nullptr;
     if (packet_counts) {
-        const int rc = stage_counts(ctx, packet_counts, n_frames, slots_per_frame, &d_counts);
+        const int rc = stage_counts(ctx, packet_counts, n_frames, slots_per_frame, d_counts);
         if (rc) return rc;
     }
     if (any_dst) {
@@ -803,7 +792,7 @@ int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const u
             ctx->shifts_w = W;
         }
     }
-    int xyzm = 0;
+    *xyzm = 0;
     if (any_xyz) {
         bool all_sep = true, none_sep = true;
         bool same = ctx->luts.p && ctx->luts_host.size() == n_luts;
@@ -819,38 +808,34 @@ int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const u
             for (uint32_t i = 0; i < n_luts; ++i) l[i] = luts[i]->dev;
             if (ensure_luts(ctx, l)) return fail(OUSTER_HIP_ERR_RUNTIME, "LUT descriptor upload failed");
         }
-        xyzm = all_sep ? (out->xyz_dtype == OUSTER_HIP_F32 ? 1 : 2) : 3;
+        *xyzm = all_sep ? (out->xyz_dtype == OUSTER_HIP_F32 ? 1 : 2) : 3;
     }
+    return OUSTER_HIP_OK;
+}
 
-    // ---- kernel arguments
-    DecodeArgs da{};
+// the kernel arguments that follow from the call's arguments alone (tile shape, mode and scratch come from the plan).
+// Returns the specialisation the kernels run with.
+static int fill_decode_args(DecodeArgs& da, ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const uint8_t* packets,
+                            size_t packet_stride, uint32_t slots_per_frame, const uint32_t* d_counts, uint32_t n_frames,
+                            const uint64_t* host_timestamps, const ouster_hip_frame_out* out, uint32_t n_luts, bool any_dst, int xyzm) {
+    const Geometry& g = fmt->g;
+    const uint32_t W = g.columns_per_frame, H = g.pixels_per_column, nf = fmt->desc.n_fields;
     da.g = g;
     da.packets = packets;
     da.packet_stride = packet_stride;
     da.slots_per_frame = slots_per_frame;
     da.n_frames = n_frames;
-    da.n_packets_out = n_packets_out;
+    da.n_packets_out = W / g.columns_per_packet;
     da.packet_counts = d_counts;
     da.host_timestamps = host_timestamps;
     da.frame_state = (uint64_t*)ctx->state.p;
     da.ready_off = FS_WORDS + (uint32_t)((ctx->state.cap / 8 - FS_WORDS) / 2);   // the second half of the buffer: moves only when it is reallocated (and zeroed)
-    if (out->xyz_poses && xyzm == 3)
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "xyz_poses need LUTs with separable tables (ouster_hip_lut_create)");
     da.xyz_poses = xyzm ? out->xyz_poses : nullptr;
-    const size_t pose_per_col = da.xyz_poses ? (size_t)12 * (xyzm == 1 ? 4 : 8) : 0;   // LDS bytes of a column's pose
     da.gate_counts = out->gate_counts;
     da.gate_min = out->gate_min_r;
     da.gate_max = out->gate_max_r;
     da.gate_field = out->gate_counts ? out->gate_field : -1;
     da.tile_valid = (uint16_t*)ctx->tile_valid.p;
-#ifdef OUSTER_PHASE_TIMING
-    {   // experiment builds only: the tool passes a device buffer's address through the environment
-        const char* e = getenv("OUSTER_HIP_PHASE_BUF");
-        da.phase_times = e ? (uint64_t*)strtoull(e, nullptr, 0) : nullptr;
-    }
-    uint64_t* const phase_times_all = da.phase_times;
-    if (getenv("OUSTER_HIP_PHASE_FIXUP_ONLY")) da.phase_times = nullptr;   // only the fix-up pass stamps
-#endif
     da.dst_offsets = (const int32_t*)ctx->offsets.p;
     da.luts = (const LutDev*)ctx->luts.p;
     da.n_luts = n_luts ? n_luts : 1;
@@ -893,370 +878,117 @@ int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const u
         if (out->xyz[0] && fmt->spec_of_desc[out->xyz_field[0]] != fmt->spec_r1) spec = SPEC_GENERIC;
         if (out->xyz[1] && fmt->spec_of_desc[out->xyz_field[1]] != fmt->spec_r2) spec = SPEC_GENERIC;
     }
+    return spec;
+}
 
-    // optimistic pass + fix-up pass when the buffer has one slot per column of the frame; everything
-    // through the general mapping otherwise
-    const bool fast = fast_possible(kn, slots_per_frame, g);
+static void set_shape(DecodeArgs& da, const TileShape& s) {
+    da.rows_per_tile = s.rows_per_tile;
+    da.row_chunks = s.row_chunks;
+    da.lds_col_slot = s.lds_col_slot;
+    da.tiles_per_frame = s.tiles_per_frame;
+    da.fix_rows_small = s.fix_rows_small;
+}
 
-    // tile width: widest tile that still lets two workgroups share a CU's 160 KiB LDS
-    int tile = 0;
-    for (int t : {64, 32, 16})
-        if (decode_lds_bytes(g, t, true, false, slots_per_frame) + 16 + t * pose_per_col <= 80 * 1024) { tile = t; break; }
-    if (!tile)
-        for (int t : {64, 32, 16})
-            if (decode_lds_bytes(g, t, true, false, slots_per_frame) + 2048 + t * pose_per_col <= 160 * 1024) { tile = t; break; }
-    if (!tile)   // the general mapping keeps resolve_frame's scratch ((2 + cpp) words per buffer slot) in LDS next to the tile
+int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const uint8_t* packets,
+                      size_t packet_stride, uint32_t slots_per_frame,
+                      const uint32_t* packet_counts, uint32_t n_frames,
+                      const uint64_t* host_timestamps, const ouster_hip_frame_out* out,
+                      const int32_t* pixel_shift_by_row, const ouster_hip_lut* const* luts,
+                      uint32_t n_luts) {
+    if (!ctx || !fmt || !out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_frames == 0) return OUSTER_HIP_OK;
+    const Geometry& g = fmt->g;
+    const uint32_t W = g.columns_per_frame, H = g.pixels_per_column, nf = fmt->desc.n_fields;
+    bool any_dst = false;
+    const bool any_xyz = (out->xyz[0] || out->xyz[1]);
+    for (uint32_t i = 0; i < nf; ++i) any_dst |= out->destaggered[i] != nullptr;
+    if (const int rc = check_decode_call(ctx, fmt, packets, packet_stride, slots_per_frame, out, pixel_shift_by_row, luts, n_luts, any_dst, any_xyz))
+        return rc;
+    hipStream_t st = ctx->stream;
+
+    const uint32_t* d_counts = nullptr;
+    int xyzm = 0;
+    if (const int rc = stage_decode_tables(ctx, fmt, slots_per_frame, packet_counts, n_frames, out, pixel_shift_by_row, luts, n_luts, any_dst,
+                                           any_xyz, &d_counts, &xyzm))
+        return rc;
+    if (out->xyz_poses && xyzm == 3)
+        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "xyz_poses need LUTs with separable tables (ouster_hip_lut_create)");
+
+    DecodeArgs da{};
+    const int spec = fill_decode_args(da, ctx, fmt, packets, packet_stride, slots_per_frame, d_counts, n_frames, host_timestamps, out, n_luts,
+                                      any_dst, xyzm);
+#ifdef OUSTER_PHASE_TIMING
+    {   // experiment builds only: the tool passes a device buffer's address through the environment
+        const char* e = getenv("OUSTER_HIP_PHASE_BUF");
+        da.phase_times = e ? (uint64_t*)strtoull(e, nullptr, 0) : nullptr;
+    }
+    uint64_t* const phase_times_all = da.phase_times;
+    if (getenv("OUSTER_HIP_PHASE_FIXUP_ONLY")) da.phase_times = nullptr;   // only the fix-up pass stamps
+#endif
+
+    // ---- the plan (decode_plan.h): which kernel, which tiles, which scratch
+    PlanInput in{};
+    in.g = g;
+    in.kn = ctx->knobs;
+    in.n_frames = n_frames;
+    in.slots_per_frame = slots_per_frame;
+    in.packet_stride = packet_stride;
+    in.packets = (uintptr_t)packets;
+    in.xyz_poses = (uintptr_t)da.xyz_poses;
+    in.spec = spec;
+    in.xyzm = xyzm;
+    in.vec_ok = da.vec_ok;
+    in.n_fields = nf;
+    for (uint32_t i = 0; i < nf; ++i) {
+        in.plane_mask |= da.planes[i] ? (1ull << i) : 0;
+        in.destagger_mask |= da.destaggered[i] ? (1ull << i) : 0;
+    }
+    in.xyz_mask = (da.xyz[0] ? 1u : 0u) | (da.xyz[1] ? 2u : 0u);
+    in.gate_counts = out->gate_counts != nullptr;
+    in.cus = ctx->cus;
+    in.resident_wgs = ctx->resident_wgs;
+#ifdef OUSTER_EXPERIMENTS
+    in.may_resolve = true;
+#else
+    in.may_resolve = false;   // k_decode_wide_resolved is not compiled
+#endif
+    const bool fast = fast_possible(in.kn, slots_per_frame, g);
+    const Candidates cand = plan_candidates(in);
+    // the tuner stands down with tune = 0 and while the stream is being captured: the default variant runs
+    TuneStep ts{256, nullptr, -1};
+    ctx->last_tuner = "none";   // forced by a knob, or a shape with nothing to choose
+    if (cand.n && in.kn.tune) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(st, &cap);
+        if (cap == hipStreamCaptureStatusNone) ts = tune_step(ctx, tuner_key(in, cand), cand.variant, cand.n);
+    }
+    DecodePlan plan = plan_decode(in, cand, ts.variant);
+    if (!plan.ok)   // the general mapping keeps resolve_frame's scratch ((2 + cpp) words per buffer slot) in LDS next to the tile
         return fail(OUSTER_HIP_ERR_UNSUPPORTED,
                     fast ? "column of %u bytes does not fit in LDS"
                          : "column of %u bytes + the column maps of %u buffer slots per frame do not fit in LDS (general mapping: at most "
                            "about 2000 slots of 16 columns; hand the frame over in fewer slots or in home slots)",
                     g.col_size, slots_per_frame);
-    // small batches: prefer narrower tiles so that at least ~2 workgroups per CU exist
-    // (one 128x2048 frame is only 32 tiles of 64 columns -- latency, not bandwidth, bound)
-    while (tile > 16 && (size_t)n_frames * ((W + tile - 1) / tile) < 512) tile /= 2;
-    if ((kn.tile == 64 || kn.tile == 32 || kn.tile == 16) &&
-        decode_lds_bytes(g, kn.tile, true, false, slots_per_frame) + 2048 + kn.tile * pose_per_col <= 160 * 1024)
-        tile = kn.tile;
-    // the per-beam xyz table goes to LDS (no vector load left in the row loop: stores are never waited
-    // for) whenever that does not cost k_decode a workgroup per CU
-    if (xyzm == 1 || xyzm == 2) {
-        const size_t extra = 2048 + tile * pose_per_col;   // fix-up frame list + pose table
-        const size_t without = decode_lds_bytes(g, tile, true, false, slots_per_frame) + extra, with = decode_lds_bytes(g, tile, true, true, slots_per_frame) + extra;
-        da.beam_lds = (kn.beam_lds && with <= 160 * 1024 && (160 * 1024) / with == (160 * 1024) / without) ? 1u : 0u;
-    }
-    // wide, short tiles (k_decode_wide): TW columns x TR rows with TW*TR*chan <= ~64 KB, TR chosen so that
-    // the row chunks are equal.  Needs a batch large enough to fill the chip; fast mode only.
-    const uint32_t narrow_tiles = (W + tile - 1) / tile;
-    // General mapping on wide tiles: the column -> slot map of every frame is resolved once (k_slotmap), not by every tile
-    const size_t resolver_lds = slotmap_lds_bytes(W, g.columns_per_packet, slots_per_frame);
-    const bool mapped_ok = !fast && kn.slotmap && kn.tile == 0 && resolver_lds <= 160 * 1024;
-    // for_fix: the tiles of the fix-up pass (k_decode_wide_fixup): resolve_frame's scratch lies under the tile image, and the
-    // grid is persistent (no minimum number of blocks)
-    // small: the tiles of the one-launch form for small batches (k_decode_wide_resolved): the scratch again, and the rows of a
-    // tile chosen so that the few frames still make about two workgroups per CU
-    auto setup_wide = [&](int want, bool for_fix = false, bool small = false) -> bool {
-        const uint32_t chan = g.channel_data_size;
-        if (!((fast || mapped_ok || small) && (want == 64 || want == 128 || want == 256 || want == 512) && chan && chan % 4 == 0 &&
-              W >= (uint32_t)want))
-            return false;
-        if ((for_fix || small) && (want == 512 || want == 64 || out->gate_counts || resolver_lds > 64 * 1024)) return false;
-        if (da.xyz_poses && ((uintptr_t)da.xyz_poses & 15u)) return false;   // the wide tiles fetch the poses in 16 B pieces
-        const uint32_t rpp = 1024u / (uint32_t)want;  // rows per pass of the 256-thread workgroup
-        uint32_t budget = (uint32_t)(kn.wide_kb > 0 ? kn.wide_kb : 64) * 1024u;
-        // with a pose table next to it the tile shrinks so that two workgroups still share a CU's LDS (a 256 x 32 tile +
-        // 12 KB of poses is 84 KB = one workgroup per CU: 1.36 ms instead of 0.7)
-        if (pose_per_col) budget = std::min<uint32_t>(budget, 72u * 1024u - (uint32_t)want * (uint32_t)pose_per_col);
-        uint32_t tr_max = budget / ((uint32_t)want * chan) / rpp * rpp;
-        tr_max = std::min(tr_max, 84u / rpp * rpp);   // k_decode_wide keeps a row chunk's table rows in registers (84 rows at most)
-        if (tr_max < rpp) return false;
-        auto up = [&](uint32_t v) { return (v + rpp - 1) / rpp * rpp; };
-        uint32_t nch = (H + tr_max - 1) / tr_max, tr = std::min(up((H + nch - 1) / nch), tr_max);
-        for (uint32_t n2 = nch; n2 <= nch + 8 && n2 <= H; ++n2) {  // prefer equal chunks
-            const uint32_t t2 = up((H + n2 - 1) / n2);
-            if (t2 <= tr_max && t2 * n2 == H && t2 * 4 >= tr * 3) { nch = n2; tr = t2; break; }   // not at the price of much smaller tiles
-        }
-        const uint32_t tiles = (W + want - 1) / want;
-        if (small) {
-            if ((size_t)n_frames * tiles * nch >= (size_t)std::max(kn.wide_min_blocks, 0)) return false;   // not a small batch
-            const uint32_t want_blocks = 2u * ctx->cus;
-            const uint32_t need = (want_blocks + n_frames * tiles - 1) / (n_frames * tiles);   // row chunks for that many workgroups
-            tr = std::max(rpp, std::min(tr, H / std::max(need, 1u) / rpp * rpp));
-        }
-        if (for_fix) {
-            // short tiles: the (few) flagged frames of a batch spread over a whole XCD instead of keeping a handful of
-            // workgroups busy for a full-height tile each (tools/ab/fixup_prof.sh: 57 us for ONE flagged frame with 32-row tiles)
-            // about 16 KB of packet bytes per tile (8 rows of 256 dual-return columns, 16 rows of 128 single-return ones): smaller
-            // tiles are all prologue (the 12 B/px profile's 128 x 8 tiles made its fix-up pass slower than r03's)
-            const uint32_t rows = kn.fixup_rows > 0 ? (uint32_t)kn.fixup_rows : (16384u + (uint32_t)want * chan - 1u) / ((uint32_t)want * chan);
-            da.fix_rows_small = std::max(rpp, std::min(tr, up(rows)));   // the launch keeps the tall tile; the kernel takes the short one for few flagged frames
-            if (tiles > 32) return false;   // the frame's ready word carries one bit per column tile
-        }
-        if (kn.wide_rows > 0) tr = std::min((uint32_t)kn.wide_rows, H);
-        if (tr > 84) return false;   // k_decode_wide keeps a row chunk's table rows in registers (3 doubles per thread) while its tile loads
-        nch = (H + tr - 1) / tr;
-        if (out->gate_counts && nch > OUSTER_HIP_GATE_CHUNKS) return false;  // one count slot per row chunk
-        if (!for_fix && !small && (size_t)n_frames * tiles * nch < (size_t)std::max(kn.wide_min_blocks, 0)) return false;
-        da.rows_per_tile = tr;
-        da.row_chunks = nch;
-        da.lds_col_slot = (tr * chan / 4 + 1) * 4;  // +1 dword: bank spread
-        da.tiles_per_frame = tiles;
-        size_t img_words = (size_t)want * (da.lds_col_slot >> 2) + 4;
-        if (for_fix || small) img_words = std::max(img_words, (resolver_lds / 4 + 3) & ~(size_t)3);
-        return decode_wide_lds_bytes(want, tr, (uint32_t)img_words) + 16 + (size_t)want * pose_per_col <= ((for_fix || small) ? 80u : 160u) * 1024;
-    };
-    // Persistent, double-buffered tiles filled by LDS-DMA (k_decode_stream): the optimistic pass of
-    // the static profiles on large batches whose buffers keep every 16 B cell's phase fixed.
-    StreamArgs sa{};
-    auto plan_field = [&](const ouster_hip_bits& b, uint32_t* dws, uint32_t& n_dw, uint32_t max_dw, FieldPlan& fp) -> bool {
-        fp.slot[0] = fp.slot[1] = fp.slot[2] = -1;
-        fp.sh = (uint8_t)((b.offset & 3u) * 8u);
-        if (b.mask == 0) return true;
-        const uint32_t lo = (uint32_t)__builtin_ctzll(b.mask) >> 3, hi = (63u - (uint32_t)__builtin_clzll(b.mask)) >> 3;
-        const uint32_t d0 = b.offset >> 2, first = (b.offset + lo) >> 2, last = (b.offset + hi) >> 2;
-        for (uint32_t d = first; d <= last; ++d) {
-            if (d - d0 > 2) return false;
-            uint32_t k = 0;
-            while (k < n_dw && dws[k] != d) ++k;
-            if (k == n_dw) {
-                if (n_dw == max_dw) return false;
-                dws[n_dw++] = d;
-            }
-            fp.slot[d - d0] = (int8_t)k;
-        }
-        return true;
-    };
-    auto setup_stream = [&](int tw) -> bool {
-        const uint32_t chan = g.channel_data_size, cpp = g.columns_per_packet;
-        if (!(fast && spec != SPEC_GENERIC && xyzm != 3 && !da.xyz_poses && vec_ok && (tw == 128 || tw == 256 || tw == 512 || tw == 1024))) return false;
-        if (W % (uint32_t)tw || (uint32_t)tw % cpp || (uint32_t)tw / cpp > 64 || chan == 0 || chan % 4) return false;
-        const uint32_t ct = W / (uint32_t)tw, per_xcd = std::max(ctx->cus / 8u, 1u);
-        if (ct > per_xcd) return false;
-        // every 16 B cell keeps its phase from tile to tile: frame bases and the frame stride are multiples of 16
-        if (((uintptr_t)packets & 15) || (((uint64_t)slots_per_frame * packet_stride) & 15)) return false;
-        // the last column's last cell must stay inside its frame's buffer
-        const uint64_t last_end = (uint64_t)(slots_per_frame - 1) * packet_stride + g.packet_header_size +
-                                  (uint64_t)(cpp - 1) * g.col_size + g.col_header_size + (uint64_t)H * chan;
-        if (last_end + 16 > (uint64_t)slots_per_frame * packet_stride) return false;
-        const uint32_t rpp = 2048u / (uint32_t)tw;   // rows per pass of the 512-thread workgroup
-        sa = StreamArgs{};
-        if (!plan_field(g.col_measurement_id, sa.hdr_dw, sa.n_hdr, 8, sa.mid) ||
-            !plan_field(g.col_status, sa.hdr_dw, sa.n_hdr, 8, sa.st) ||
-            !plan_field(g.col_timestamp, sa.hdr_dw, sa.n_hdr, 8, sa.ts) ||
-            !plan_field(g.alert_flags, sa.pkt_dw, sa.n_pkt, 4, sa.alert))
-            return false;
-        auto fits = [&](uint32_t tr) -> bool {
-            if (tr == 0 || tr % rpp || H % tr || (tr * chan) % 16) return false;
-            sa.tr = tr;
-            sa.nch = H / tr;
-            sa.ncell = tr * chan / 16 + 1;
-            sa.npix_instr = ((uint32_t)tw * sa.ncell + 63) / 64;
-            if (sa.npix_instr > 72) return false;
-            uint32_t o = sa.npix_instr * 1024u;
-            sa.hdr_off = o; o += sa.n_hdr * (uint32_t)tw * 4u;
-            sa.pkt_off = o; o += 6u * 256u;
-            sa.off_off = o; o += ((tr + 63) / 64) * 256u;
-            sa.beam_off = o; o += ((tr * 18u + 63) / 64) * 256u;
-            sa.ctx_bytes = (o + 1023u) & ~1023u;
-            sa.fixed_off = 2u * sa.ctx_bytes;
-            sa.lds_bytes = sa.fixed_off + 3u * (uint32_t)tw * 4u + 32u;
-            return sa.lds_bytes <= 160u * 1024u;
-        };
-        bool ok = false;
-        if (kn.stream_rows > 0) ok = fits((uint32_t)kn.stream_rows);
-        else
-            for (uint32_t tr = H / rpp * rpp; tr >= rpp && !ok; tr -= rpp) ok = fits(tr);   // the tallest tile that fits twice
-        if (!ok) return false;
-        if (out->gate_counts && sa.nch > OUSTER_HIP_GATE_CHUNKS) return false;
-        sa.groups = per_xcd / ct;
-        const uint64_t tiles = (uint64_t)n_frames * ct * sa.nch, wgs = 8ull * ct * sa.groups;
-        if (kn.stream_min_tiles > 0 && tiles < wgs * (uint64_t)kn.stream_min_tiles) return false;
-        // stores a wave issues per tile (one per output stream and lane row): with at least 63 of them behind a
-        // prefetch the 6-bit in-order vmcnt itself proves the prefetch has landed
-        uint32_t streams = 0;
-        for (uint32_t i = 0; i < nf; ++i) streams += (da.planes[i] ? 1u : 0u) + (da.destaggered[i] ? 1u : 0u);
-        for (int k = 0; k < 2; ++k)
-            if (da.xyz[k]) streams += xyzm == 1 ? 3u : 6u;
-        const uint32_t stores_per_wave = streams * (sa.tr / rpp);
-        sa.wait0 = (kn.stream_wait == 0 && stores_per_wave >= 64) ? 0u : 1u;
-        sa.order = (uint32_t)kn.stream_order;
-        sa.loader = (kn.stream_loader > 0 && (tw == 128 || tw == 256) && !out->gate_counts && kn.stream_order == 0)
-                        ? (uint32_t)std::min(kn.stream_loader, 4) : 0u;
-        da.rows_per_tile = sa.tr;
-        da.row_chunks = sa.nch;
-        da.lds_col_slot = 0;
-        da.tiles_per_frame = ct;
-        return true;
-    };
-    // Which optimistic-pass kernel?  Forced by a knob, or -- large batches of a static profile -- timed: k_decode_wide
-    // 256 x R, 128 x R, k_decode's 64-column tiles and (where the buffers allow it) the persistent k_decode_stream.
-    // Which one wins depends on how the buffers happen to lie in HBM: the persistent kernel is
-    // 1.5 - 3 % ahead where the memory system is fastest and up to 10 % behind where it is slowest.
-    int stream = 0, wide = 0;
-    int stream_auto = 0;   // tile width of the persistent candidate (0: not eligible)
-    int stream_alt = 0;    // ... and of the other width, when that is eligible too (round 4: the 12 B/px profile's 256 x 16 tiles
-                           // beat its 128 x 32 ones by 3 - 4 % on some boxes, tools/ab/single_variants.py)
-    // Small batches (one tick of a few sensors, a single frame): one launch, every wide tile resolves its frame's column maps
-    // itself -- neither an optimistic pass nor a second launch, whatever the buffer looks like.
-    // Measured (tools/ab/small_batch.py, 4 x 128 x 2048 dual return): optimistic wide tiles of 8 rows + the fix-up launch 27 us
-    // per call, k_decode's 16-column tiles + fix-up 33 us, the one-launch form 35 us (its workgroups resolve the frame
-    // before they can start: 14 us against the 3 us a second launch costs).  So: a buffer with one slot per column takes the
-    // optimistic wide tiles, any other shape the one-launch form (kn.small = 2 forces it for both).
-    bool resolved = false, small_wide = false;
-#ifdef OUSTER_EXPERIMENTS
-    constexpr bool may_resolve = true;
-#else
-    constexpr bool may_resolve = false;   // default build: a small batch whose buffer is not "one slot per column" takes the general
-                                          // mapping like a large one (k_slotmap + k_decode_wide); k_decode_wide_resolved is not compiled
-#endif
-    if (kn.small && kn.stream <= 0 && kn.wide < 0 && kn.tile == 0 && kn.fast && (fast || may_resolve)) {
-        for (int tw : {256, 128})
-            if (W >= (uint32_t)tw) {
-                if (setup_wide(tw, false, true)) {
-                    wide = tw;
-                    resolved = may_resolve && (!fast || kn.small == 2);
-                    small_wide = !resolved;
-                }
-                break;
-            }
-    }
-    if (resolved || small_wide) {
-        // nothing else to choose
-    } else if (kn.stream > 0) {
-        if (setup_stream(kn.stream)) stream = kn.stream;
-    } else if (kn.stream < 0 && kn.wide < 0 && kn.tile == 0) {
-        // column pieces of at least 256 B per tile row chunk: 256 columns for the 8 / 16 / 4 B/px profiles, 128 for 12 B/px
-        if (setup_stream(256) && sa.tr * g.channel_data_size >= 256) stream_auto = 256;
-        else if (setup_stream(128)) stream_auto = 128;
-        else if (setup_stream(256)) stream_auto = 256;
-        if (stream_auto) {
-            const int other = stream_auto == 256 ? 128 : 256;
-            if (setup_stream(other)) stream_alt = other;
-        }
-    }
-    ouster_hip_ctx::Tune* tuning = nullptr;
-    int tune_slot = -1;
-    ctx->last_tuner = "none";   // forced by a knob, or a shape with nothing to choose
-    if (stream || resolved || small_wide) {
-        // forced / nothing to choose
-    } else if (kn.wide >= 0) {  // forced (experiments, tests)
-        if (kn.wide && setup_wide(kn.wide)) wide = kn.wide;
-    } else if (!fast) {
-        // general mapping on wide tiles (k_slotmap first): column pieces of at least 256 B, like the persistent kernel's choice
-        if (setup_wide(256) && da.rows_per_tile * g.channel_data_size >= 256) wide = 256;
-        else if (setup_wide(128)) wide = 128;
-        else if (setup_wide(256)) wide = 256;
-    } else if (setup_wide(256)) {
-        int sel = 256;   // >= 1000: the persistent kernel with tile width sel - 1000
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(st, &cap);
-        if (kn.tune && cap == hipStreamCaptureStatusNone) {
-            uint64_t key = 1469598103934665603ull;
-            auto mix = [&](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
-            uint32_t lg = 0;  // batches of similar size share a verdict
-            while ((2u << lg) <= n_frames) ++lg;
-            mix((uint64_t)spec); mix(W); mix(H); mix(g.channel_data_size); mix(lg); mix((uint64_t)xyzm);
-            uint64_t pm = 0, dm = 0;
-            for (uint32_t i = 0; i < nf; ++i) {
-                pm |= da.planes[i] ? (1ull << i) : 0;
-                dm |= da.destaggered[i] ? (1ull << i) : 0;
-            }
-            mix(pm); mix(dm);
-            mix((da.xyz[0] ? 1u : 0u) | (da.xyz[1] ? 2u : 0u) | (da.gate_counts ? 4u : 0u) | (da.xyz_poses ? 8u : 0u));
-            mix((uint64_t)stream_auto); mix((uint64_t)stream_alt);
-            if (ctx->tune.size() > 64 && !ctx->tune.count(key)) {  // bounded: forget everything, re-learn
-                for (auto& kv : ctx->tune)
-                    for (auto& pr : kv.second.ev)
-                        for (hipEvent_t e : pr)
-                            if (e) (void)hipEventDestroy(e);
-                ctx->tune.clear();
-            }
-            const bool fresh = !ctx->tune.count(key);
-            ouster_hip_ctx::Tune& t = ctx->tune[key];
-            const int cand[ouster_hip_ctx::Tune::NCAND] = {256, 128, 0, 1000 + stream_auto, 1000 + stream_alt};
-            const int nc = stream_auto ? (stream_alt ? 5 : 4) : 3;
-            if (fresh) {   // an earlier process (or rank) has timed this workload on this device: launch its choice from call 1
-                auto hit = ctx->tune_cache.find(key);
-                if (hit != ctx->tune_cache.end()) {
-                    bool known = false;
-                    for (int c = 0; c < nc; ++c) known = known || cand[c] == hit->second;
-                    if (known) { t.best = hit->second; t.from_cache = true; }
-                }
-            }
-            // Four launches of each candidate, back to back (a launch that follows a different variant
-            // is not representative of the steady state: alternating the candidates made the 64-column
-            // kernel look 8 % faster than it then ran).  Single launches vary by ~10 %, mostly upwards,
-            // and the candidates can be within 1-5 % of each other: each candidate's fastest sample
-            // counts, its first one (cold code, cold TLB, another variant's write-backs still draining)
-            // only when nothing else landed.  The clocks are polled, never waited for: until all samples
-            // have landed the default variant runs.
-            constexpr int R = ouster_hip_ctx::Tune::ROUNDS;
-            const int NS = nc * R;
-            if (t.best == -2 && t.calls >= NS) {
-                bool all = true;
-                for (int i = 0; i < NS && all; ++i) all = hipEventQuery(t.ev[i][1]) == hipSuccess;
-                if (!all) (void)hipGetLastError();
-                else {
-                    float cold[ouster_hip_ctx::Tune::NCAND] = {0, 0, 0, 0, 0};
-                    for (int i = 0; i < NS; ++i) {
-                        float ms = 0;
-                        if (hipEventElapsedTime(&ms, t.ev[i][0], t.ev[i][1]) != hipSuccess || ms <= 0) continue;
-                        float& slot = (i % R == 0) ? cold[i / R] : t.ms[i / R];
-                        if (slot == 0 || ms < slot) slot = ms;
-                    }
-                    for (int c = 0; c < nc; ++c)
-                        if (t.ms[c] == 0) t.ms[c] = cold[c];
-                    t.best = 256;
-                    float best_ms = 0;
-                    for (int c = 0; c < nc; ++c)
-                        if (t.ms[c] > 0 && (best_ms == 0 || t.ms[c] < best_ms)) { t.best = cand[c]; best_ms = t.ms[c]; }
-                    tune_cache_append(ctx, key, t.best, best_ms);
-                }
-            }
-            if (t.best != -2) {
-                sel = t.best;
-                ctx->last_tuner = t.from_cache ? "cache" : "measured";
-            } else if (t.calls < NS) {
-                tune_slot = t.calls;
-                sel = cand[tune_slot / R];
-                tuning = &t;
-                ++t.calls;
-                ctx->last_tuner = "measuring";
-            } else {
-                ctx->last_tuner = "measuring";   // every sample is queued, not all have landed: the default variant runs
-            }
-        }
-        if (sel >= 1000 && setup_stream(sel - 1000)) stream = sel - 1000;
-        else if (sel > 0 && sel < 1000 && setup_wide(sel)) wide = sel;
-        else if (sel != 0 && setup_wide(256)) wide = 256;
-    }
-    if (!wide && !stream) {
-        da.rows_per_tile = da.row_chunks = da.lds_col_slot = 0;
-        da.tiles_per_frame = narrow_tiles;
-    }
-    da.xcd_map = (kn.xcd && n_frames >= 8) ? 1u : 0u;
-    da.mode = resolved ? MODE_RESOLVED : fast ? MODE_FAST : MODE_GENERAL;
-    if (resolved) ctx->state_dirty = false;   // this call leaves the frame words alone
 
-    // ---- the fix-up pass behind an optimistic pass: the tiles of the frames the optimistic pass flagged are looked at again
-    // with the frame's real column maps and redone where those differ from "slot c holds column c".  Wide tiles
-    // (fixup_crew, wide_tile.h) where the format allows them, k_decode_fixup's 64-column tiles otherwise.  Always launched
-    // behind the optimistic kernel; the workgroups of a clean batch leave after two scalar loads (FS_ANY).  Its tile shape and
-    // every allocation of the call are settled here, before the first launch.
-    struct Shape { uint32_t rows, chunks, slot, tiles, rows_small; };
-    auto shape_now = [&]() { return Shape{da.rows_per_tile, da.row_chunks, da.lds_col_slot, da.tiles_per_frame, da.fix_rows_small}; };
-    auto shape_set = [&](const Shape& sh) {
-        da.rows_per_tile = sh.rows; da.row_chunks = sh.chunks; da.lds_col_slot = sh.slot; da.tiles_per_frame = sh.tiles; da.fix_rows_small = sh.rows_small;
-    };
-    const Shape opt = shape_now();
-    const bool want_fix = fast && kn.fixup && !resolved;
-    int fix_wide = 0;
-    Shape fixs{};
-    if (want_fix) {
-        auto try_fix = [&](int tw) {
-            const bool ok = setup_wide(tw, true);
-            if (ok) { fix_wide = tw; fixs = shape_now(); }
-            shape_set(opt);
-            return ok;
-        };
-        if (kn.fixup_wide && kn.tile == 0) {
-            if (kn.fixup_wide > 1) try_fix(kn.fixup_wide);
-            else if (setup_wide(256, true) && da.rows_per_tile * g.channel_data_size >= 256) try_fix(256);
-            else if (!try_fix(128)) try_fix(256);
-            shape_set(opt);
-        }
-        if (kn.hdr_words) {   // the optimistic pass leaves the packed column ids for the fix-up pass
-            if (ctx->hdrw.ensure((size_t)n_frames * W * sizeof(uint32_t))) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (header words)");
-            da.hdr_words = (uint32_t*)ctx->hdrw.p;
-        }
-        if (fix_wide && ctx->slotmap.ensure((size_t)n_frames * W * sizeof(int32_t) * 2)) fix_wide = 0;   // the 64-column fix-up needs no maps
-        da.fast_tiles = opt.tiles;    // column tiles of the optimistic pass (slots of tile_valid)
+    // ---- every allocation of the call is settled here, before the first launch
+    if (plan.hdr_words_bytes) {
+        if (ctx->hdrw.ensure(plan.hdr_words_bytes)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (header words)");
+        da.hdr_words = (uint32_t*)ctx->hdrw.p;
     }
-    if (wide && !fast && !resolved) {
-        if (ctx->slotmap.ensure((size_t)n_frames * W * sizeof(int32_t) * 2)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (slot map)");
+    if (plan.fixup == Fixup::WIDE && ctx->slotmap.ensure(plan.slotmap_bytes)) demote_fixup(in, plan);   // the 64-column fix-up needs no maps
+    if (plan.slotmap) {
+        if (ctx->slotmap.ensure(plan.slotmap_bytes)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (slot map)");
         da.slot_map = (int32_t*)ctx->slotmap.p;
         da.hdr_map = da.slot_map + (size_t)n_frames * W;
     }
+    set_shape(da, plan.shape);
+    da.beam_lds = plan.beam_lds;
+    da.xcd_map = plan.xcd_map;
+    da.mode = plan.mode;
+    da.fast_tiles = plan.fast_tiles;
+    if (plan.mode == MODE_RESOLVED) ctx->state_dirty = false;   // this call leaves the frame words alone
 
+    // ---- the optimistic (or only) pass
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (ctx->timing && (ctx->timing_calls++ % ctx->timing_every) == 0) {
         if (ctx->ev_used == ctx->ev_pool.size()) {
@@ -1270,49 +1002,50 @@ int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const u
         ctx->ev_used++;
         HIP_TRY(hipEventRecord(e0, st));
     }
-    if (tuning) {
+    if (ts.record) {
         for (int k = 0; k < 2; ++k)
-            if (!tuning->ev[tune_slot][k]) HIP_TRY(hipEventCreate(&tuning->ev[tune_slot][k]));
-        HIP_TRY(hipEventRecord(tuning->ev[tune_slot][0], st));
+            if (!ts.record->ev[ts.slot][k]) HIP_TRY(hipEventCreate(&ts.record->ev[ts.slot][k]));
+        HIP_TRY(hipEventRecord(ts.record->ev[ts.slot][0], st));
     }
-    if (wide && !fast && !resolved) HIP_TRY(launch_slotmap(da, ctx->device, st));
-    if (stream) {
-        HIP_TRY(launch_decode_stream(da, sa, spec, stream, xyzm, ctx->device, st));
-        ctx->last_tile_cols = stream;
-        ctx->last_tile_rows = (int)sa.tr;
-        ctx->last_kernel = sa.loader ? "k_decode_stream2" : "k_decode_stream";   // dedicated loader waves / every wave fetches
-    } else if (wide) {
-        HIP_TRY(launch_decode_wide(da, spec, wide, xyzm, ctx->device, st));
-        ctx->last_tile_cols = wide;
-        ctx->last_tile_rows = (int)opt.rows;
-        ctx->last_kernel = resolved ? "k_decode_wide_resolved" : "k_decode_wide";
-    } else {
-        HIP_TRY(launch_decode(da, spec, tile, xyzm, ctx->device, st));
-        ctx->last_tile_cols = tile;
-        ctx->last_tile_rows = (int)H;
-        ctx->last_kernel = "k_decode";
+    if (plan.slotmap) HIP_TRY(launch_slotmap(da, ctx->device, st));
+    switch (plan.kernel) {
+        case Kernel::STREAM:
+        case Kernel::STREAM2:
+            HIP_TRY(launch_decode_stream(da, plan.sa, spec, plan.cols, xyzm, ctx->device, st));
+            ctx->last_tile_rows = (int)plan.sa.tr;
+            break;
+        case Kernel::WIDE:
+        case Kernel::WIDE_RESOLVED:
+            HIP_TRY(launch_decode_wide(da, spec, plan.cols, xyzm, ctx->device, st));
+            ctx->last_tile_rows = (int)plan.shape.rows_per_tile;
+            break;
+        case Kernel::DECODE:
+            HIP_TRY(launch_decode(da, spec, plan.narrow_tile, xyzm, ctx->device, st));
+            ctx->last_tile_rows = (int)H;
+            break;
     }
-    if (tuning) HIP_TRY(hipEventRecord(tuning->ev[tune_slot][1], st));
+    ctx->last_tile_cols = plan.cols;
+    ctx->last_kernel = kernel_name(plan.kernel);
+    if (ts.record) HIP_TRY(hipEventRecord(ts.record->ev[ts.slot][1], st));
     if (e1) HIP_TRY(hipEventRecord(e1, st));
-    if (want_fix) {
+
+    // ---- the fix-up pass: always launched behind an optimistic kernel; the workgroups of a clean batch leave after two
+    // scalar loads (FS_ANY)
+    if (plan.fixup != Fixup::NONE) {
         da.mode = MODE_FIXUP;
 #ifdef OUSTER_PHASE_TIMING
         da.phase_times = phase_times_all;
 #endif
-        if (fix_wide) {
-            shape_set(fixs);
+        set_shape(da, plan.fix_shape);
+        if (plan.fixup == Fixup::WIDE) {
             da.slot_map = (int32_t*)ctx->slotmap.p;
             da.hdr_map = da.slot_map + (size_t)n_frames * W;
-            HIP_TRY(launch_decode_wide(da, spec, fix_wide, xyzm, ctx->device, st, ctx->resident_wgs));
+            HIP_TRY(launch_decode_wide(da, spec, plan.fix_cols, xyzm, ctx->device, st, ctx->resident_wgs));
         } else {
-            da.rows_per_tile = 0;
-            da.lds_col_slot = 0;
-            da.row_chunks = ctx->resident_wgs;     // persistent grid: what the device keeps resident
-            da.tiles_per_frame = narrow_tiles;
-            HIP_TRY(launch_decode(da, spec, tile, xyzm, ctx->device, st));
+            HIP_TRY(launch_decode(da, spec, plan.narrow_tile, xyzm, ctx->device, st));
         }
+        ctx->state_dirty = false;
     }
-    if (want_fix) ctx->state_dirty = false;
     return OUSTER_HIP_OK;
 }
 

@@ -7,19 +7,9 @@
 #include <utility>
 
 #include "../../include/ouster_hip.h"
+#include "decode_plan.h"   // Geometry, StreamArgs, DecodeMode, FS_*, the LDS sizes: what the launch plan needs, HIP-free
 
 namespace ouster_hip_dev {
-
-enum SpecId { SPEC_GENERIC = 0, SPEC_DUAL_LB, SPEC_LB, SPEC_SINGLE, SPEC_DUAL, SPEC_LEGACY };
-
-struct Geometry {
-    uint32_t pixels_per_column, columns_per_packet, columns_per_frame;
-    uint32_t packet_header_size, col_header_size, channel_data_size, col_footer_size,
-        packet_footer_size, col_size, lidar_packet_size;
-    ouster_hip_bits col_timestamp, col_measurement_id, col_status;
-    ouster_hip_bits frame_id, alert_flags, thermal_shutdown, shot_limiting,
-        countdown_thermal_shutdown, countdown_shot_limiting;
-};
 
 // device view of one XYZ lookup table
 struct LutDev {
@@ -31,19 +21,6 @@ struct LutDev {
     int32_t full_dtype;      // OUSTER_HIP_F32 / F64 for full_dir/full_ofs, 0 when separable
     int32_t pad;
 };
-
-// how a decode launch finds the source column of a destination column
-enum DecodeMode : uint32_t {
-    MODE_FAST = 0,     // optimistic: slot s holds column s; verified against the staged headers, strays
-                       //   flag their frame in frame_state
-    MODE_FIXUP = 1,    // second pass: redo the frames the fast pass flagged (the others return at once)
-    MODE_GENERAL = 2,  // every frame through the scan-the-frame path (slots_per_frame*cpp != W)
-    MODE_RESOLVED = 3, // small batches, one launch: every wide tile resolves its frame's column maps itself (k_decode_wide_resolved)
-};
-
-// frame_state words (kernels_common.h): sequence, tag, 2 x 8 ticket counters, the launch-wide "a frame was flagged" word
-// (its own cache line: only ever touched by atomics), then one word per frame (from a line boundary on)
-constexpr uint32_t FS_SEQ = 0, FS_TAG = 1, FS_TICKET = 2, FS_ANY = 20, FS_WORDS = 32;
 
 // fix-up crew (wide_tile.h): frames listed per round, and the crew's bookkeeping in dynamic LDS (DecodeArgs::crew_lds_off)
 constexpr uint32_t FIXUP_CHUNK = 512;
@@ -114,31 +91,6 @@ struct DecodeArgs {
 #ifdef OUSTER_PHASE_TIMING
     uint64_t* phase_times;   // experiment builds only (tools/ab/phase_timing.sh): [workgroup][8] s_memtime stamps of k_decode_wide
 #endif
-};
-
-// k_decode_stream (persistent, double-buffered tiles filled by LDS-DMA): what the host works out
-// once per launch.  A tile context in LDS = the pixel image (TW column blocks of `ncell` 16 B cells, block of column j at
-// index j/4 + (TW/4)*(j%4)), then the column-header dwords [n_hdr][TW], the packet-level dwords [n_pkt + 2][64], the
-// destagger offsets of the tile's rows and their per-beam xyz constants.
-struct FieldPlan {   // a 64-bit field window assembled from fetched dwords: window dword k comes from slot[k] (-1: not needed)
-    int8_t slot[3];
-    uint8_t sh;      // bit position of the window inside window dword 0
-};
-struct StreamArgs {
-    uint32_t tr, nch;          // rows per tile, row chunks per frame
-    uint32_t ncell;            // 16 B cells per column block (the piece of tr rows plus its 16 B phase)
-    uint32_t npix_instr;       // 1 KB wave-instructions that fill the pixel image
-    uint32_t hdr_off, pkt_off, off_off, beam_off, ctx_bytes;  // byte offsets inside a tile context / its size
-    uint32_t fixed_off;        // byte offset of the per-workgroup tables behind the two contexts
-    uint32_t n_hdr, n_pkt;     // dwords fetched per column / per packet
-    uint32_t hdr_dw[8];        //   their dword offsets from the column start
-    uint32_t pkt_dw[4];        //   ... from the packet start
-    FieldPlan mid, st, ts, alert;
-    uint32_t groups;           // workgroups per (XCD, column tile)
-    uint32_t wait0;            // 1: vmcnt(0) before a prefetched tile is used; 0: rely on the in-order counter (>= 63 stores since)
-    uint32_t lds_bytes;
-    uint32_t order;            // how a group walks the XCD's (frame, row chunk) items, see the kernel
-    uint32_t loader;           // > 0: k_decode_stream2 with that many loader waves behind the eight decoding ones (1..4)
 };
 
 struct DestaggerArgs {
@@ -218,14 +170,10 @@ struct FieldC {
 };
 const FieldC* spec_fields(int spec_id, int* nf, uint32_t* chan, int* r1, int* r2);
 
-// LDS of one k_decode workgroup (the general modes add the per-frame packet map and valid bitmap)
-size_t decode_lds_bytes(const Geometry& g, int tile, bool general, bool beam_lds, uint32_t slots_per_frame = 0);
-size_t decode_wide_lds_bytes(int tw, uint32_t rows_per_tile, uint32_t img_words);
 // device: HIP device ordinal of the stream (per-device cache of the one-off kernel attributes)
 hipError_t launch_decode(const DecodeArgs& a, int spec_id, int tile, int xyzm, int device, hipStream_t st);
 hipError_t launch_decode_wide(const DecodeArgs& a, int spec_id, int tw, int xyzm, int device, hipStream_t st, uint32_t resident = 0);
 hipError_t launch_decode_stream(const DecodeArgs& a, const StreamArgs& sp, int spec_id, int tw, int xyzm, int device, hipStream_t st);
-size_t slotmap_lds_bytes(uint32_t W, uint32_t cpp, uint32_t slots_per_frame);   // resolve_frame's LDS scratch
 hipError_t launch_slotmap(const DecodeArgs& a, int device, hipStream_t st);
 hipError_t launch_destagger(const DestaggerArgs& a, uint32_t n_images, hipStream_t st);
 hipError_t launch_cartesian(const CartesianArgs& a, int mode, hipStream_t st);
