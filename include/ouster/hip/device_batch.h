@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "ouster/core/image_processing.h"
 #include "ouster/core/lidar_frame.h"
 #include "ouster/core/xyzlut.h"
 #include "ouster/hip/context.h"
@@ -70,6 +71,16 @@ struct BatchOptions {
     std::string tuning_cache;
     int device = -1;                      ///< GPU to work on (-1: hip::current_device() of the constructing thread)
     std::shared_ptr<Context> context;     ///< share this context (stream + scratch) instead of owning one
+};
+
+/** Display-image state of a batch's sensors (DeviceFrameBatch::render_images): one AutoExposure per sensor and, unless
+ *  switched off, one BeamUniformityCorrector in front of it -- what a caller of the reference keeps per sensor next to its
+ *  `buc.update(img); ae.update(img)` lines.  The objects are public: construct them differently by assigning. */
+struct ImagePipeline {
+    explicit ImagePipeline(size_t n_sensors, bool beam_uniformity = true)
+        : auto_exposure(n_sensors), beam_uniformity(beam_uniformity ? n_sensors : 0) {}
+    std::vector<core::image::AutoExposure> auto_exposure;
+    std::vector<core::image::BeamUniformityCorrector> beam_uniformity;   ///< empty: no correction
 };
 
 class DeviceFrameBatch {
@@ -156,6 +167,16 @@ class DeviceFrameBatch {
     void download_xyz(int return_index, uint32_t frame, void* host);
     void download_headers(uint32_t frame, uint64_t* timestamp, uint16_t* measurement_id, uint32_t* status);
 
+    /** Display images of the whole decoded batch without leaving HBM: the destaggered plane of `field` (it must be listed in
+     *  BatchOptions::destagger -- @throw std::invalid_argument otherwise) of every frame goes through its sensor's
+     *  BeamUniformityCorrector (if the pipeline has one) and AutoExposure: frame f belongs to sensor f % sensors, each
+     *  sensor's frames are processed in index order with the reference's state machine (core/image_processing.h).  Returns the
+     *  device pointer of the result, float [n_frames][h][w], owned by the batch (allocated on the first call for `field`).
+     *  Three kernel launches and two small round trips per sensor; synchronous. */
+    void* render_images(const std::string& field, ImagePipeline& pipe, bool update_state = true);
+    /** One frame's image of the last render_images(field, ...) (h * w floats; synchronous). */
+    void download_image(const std::string& field, uint32_t frame, float* host);
+
     /** Per-column body_to_world poses of one frame (w x 16 doubles, row-major 4x4 each; identity
      *  until set), the input of dewarp(). */
     void upload_poses(uint32_t frame, const double* poses_w_by_16);
@@ -183,6 +204,8 @@ class DeviceFrameBatch {
     std::shared_ptr<Context> ctx_;
     core::PacketFormat pf_;
     uint32_t n_frames_, h_, w_, slots_;
+    uint32_t n_sensors_ = 1;
+    std::map<std::string, DeviceBuffer> d_images_;   // render_images: float [n_frames][h][w] per field, made on first use
     size_t stride_;
     BatchOptions opt_;
     std::vector<std::pair<std::string, uint32_t>> fields_;

@@ -431,8 +431,56 @@ int ouster_hip_dewarp_host(ouster_hip_ctx* ctx, const void* points, const double
 int ouster_hip_copy_in(ouster_hip_ctx* ctx, void* dev_dst, const void* host_src, size_t bytes);
 int ouster_hip_copy_out(ouster_hip_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes);
 /* Grow-only device scratch owned by the context (slot 0..7; contents undefined; valid until the same slot is
- * asked for more).  What the *_host calls stage through; bindings that stage themselves use slots 4..7. */
+ * asked for more).  What the *_host calls stage through (0..3); bindings that stage themselves use slots 4..7, and so do the
+ * C++ mirror's AutoExposure / BeamUniformityCorrector::update_batch (synchronous: nothing is kept there across calls). */
 int ouster_hip_ctx_scratch(ouster_hip_ctx* ctx, uint32_t slot, size_t bytes, void** out);
+
+/* ---- display images: BeamUniformityCorrector / AutoExposure -------------------------------------- */
+/* The device half of ouster::sdk::core::image::BeamUniformityCorrector and AutoExposure, single-channel overloads
+ * (ouster_core/include/ouster/core/image_processing.h:25-165, src/image_processing.cpp:220-296 and :427-498), batched:
+ * n_images images of h x w elements, image i at planes + i * image_stride elements (0: dense, h * w).  in_type is U8, U16,
+ * U32 (converted to the image type on load, round to nearest even, like astype / static_cast) or equal to out_type;
+ * out_type (F32 / F64) is the type T the reference would be called with: every value below is computed in T, bit for bit.
+ * The frame-to-frame state (exponential smoothing, counters, the choice of the map) stays with the caller, in double, as
+ * in the reference -- include/ouster/core/image_processing.h holds it.  n_images <= 65535, h * w <= 2^31.
+ *
+ * ouster_hip_image_dark_rows: the order statistics of compute_dark_count (:427-460).  Over the columns that hold at least one
+ *   pixel != 0 (n_cols of them), for every row i >= 1 the n_cols / 2-th smallest of image(i, c) - image(i - 1, c):
+ *   medians [n_images][h - 1] of T (all 0 when n_cols == 0), n_cols [n_images] (nullable).  w <= 4096 (UNSUPPORTED beyond);
+ *   a non-empty image with h < 2 has no row pair: INVALID_ARGUMENT (n_images, h or w == 0: OK, nothing is written).
+ * ouster_hip_image_percentiles: the order statistics of AutoExposure::apply (:224-252).  The sample is every 4th element of the
+ *   flat image, with `dark` (T [n_images][h], nullable) first corrected to max(x - dark[row], 0), kept when > 0:
+ *   n [n_images] = its size, lo_hi [n_images][2] of T = its floor(n * lo_percentile)-th and (n - floor(n * hi_percentile) - 1)-th
+ *   smallest values (0, 0 when n == 0).  n < 100 is reported like any other n: the caller decides.
+ *   Needs lo_percentile + hi_percentile < 1 and no NaN in the image (the reference is undefined outside this).
+ * ouster_hip_image_apply: out(i) = map(max(in(i) - dark[row], 0)) per image: `dark` as above (nullable), maps [n_images] DEVICE
+ *   array (nullable: no map).  out may be planes itself when in_type == out_type (in place). */
+#define OUSTER_HIP_IMAGE_MAP_NONE 0    /* no map, no clamp to [0, 1]: AutoExposure's early return, or a BeamUniformityCorrector alone */
+#define OUSTER_HIP_IMAGE_MAP_SCALE 1   /* x * T(mul), clamped to [0, 1] */
+#define OUSTER_HIP_IMAGE_MAP_AFFINE 2  /* ((x - T(sub)) * T(mul)) + T(add), each step rounded, clamped to [0, 1] */
+typedef struct ouster_hip_image_map {
+    int32_t mode;      /* OUSTER_HIP_IMAGE_MAP_* */
+    int32_t use_dark;  /* 0: this image skips the dark-count correction */
+    double sub, mul, add;
+} ouster_hip_image_map;
+int ouster_hip_image_dark_rows(ouster_hip_ctx* ctx, const void* planes, int in_type, int out_type, uint32_t n_images,
+                               uint32_t h, uint32_t w, size_t image_stride, void* medians, uint32_t* n_cols);
+int ouster_hip_image_percentiles(ouster_hip_ctx* ctx, const void* planes, int in_type, int out_type, uint32_t n_images,
+                                 uint32_t h, uint32_t w, size_t image_stride, const void* dark, double lo_percentile,
+                                 double hi_percentile, uint32_t* n, void* lo_hi);
+int ouster_hip_image_apply(ouster_hip_ctx* ctx, const void* planes, int in_type, void* out, int out_type, uint32_t n_images,
+                           uint32_t h, uint32_t w, size_t in_stride, size_t out_stride, const void* dark,
+                           const ouster_hip_image_map* maps);
+/* The same on ONE host image of type T (`dtype`, F32 / F64), results in HOST memory when the call returns: pool memory
+ * (ouster_hip_host_alloc) is worked on in place, other memory goes through the context's scratch.  dark: HOST T [h] (nullable);
+ * map: HOST record (nullable).  ouster_hip_image_apply_host works in place. */
+int ouster_hip_image_dark_rows_host(ouster_hip_ctx* ctx, const void* image, int dtype, uint32_t h, uint32_t w, void* medians,
+                                    uint32_t* n_cols);
+int ouster_hip_image_percentiles_host(ouster_hip_ctx* ctx, const void* image, int dtype, uint32_t h, uint32_t w,
+                                      const void* dark, double lo_percentile, double hi_percentile, uint32_t* n,
+                                      void* lo_hi);
+int ouster_hip_image_apply_host(ouster_hip_ctx* ctx, void* image, int dtype, uint32_t h, uint32_t w, const void* dark,
+                                const ouster_hip_image_map* map);
 
 /* ---- instrumentation ------------------------------------------------------ */
 /* Average duration in ms of the dominant decode kernel over the launches made

@@ -74,6 +74,14 @@ class OsfPlane(C.Structure):
                 ("dst_elem_size", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class ImageMap(C.Structure):
+    """ouster_hip_image_map (include/ouster_hip.h): the per-image record of ouster_hip_image_apply"""
+    _fields_ = [("mode", C.c_int32), ("use_dark", C.c_int32), ("sub", C.c_double), ("mul", C.c_double), ("add", C.c_double)]
+
+
+IMAGE_MAP_NONE, IMAGE_MAP_SCALE, IMAGE_MAP_AFFINE = 0, 1, 2
+
+
 # every symbol include/ouster_hip.h declares (checked by tests/test_abi.py)
 class AllocStats(C.Structure):
     """ouster_hip_alloc_stats (include/ouster_hip.h)"""
@@ -94,6 +102,9 @@ ABI_SYMBOLS = [
     "ouster_hip_destagger_host", "ouster_hip_cartesian_host", "ouster_hip_dewarp_host",
     "ouster_hip_copy_in", "ouster_hip_copy_out", "ouster_hip_ctx_scratch",
     "ouster_hip_ctx_set_tuning_cache", "ouster_hip_last_decode_tuner",
+    # display images: the device half of BeamUniformityCorrector / AutoExposure
+    "ouster_hip_image_dark_rows", "ouster_hip_image_percentiles", "ouster_hip_image_apply",
+    "ouster_hip_image_dark_rows_host", "ouster_hip_image_percentiles_host", "ouster_hip_image_apply_host",
 ]
 
 _hip = None
@@ -187,6 +198,15 @@ def load_hip(private_path: Optional[str] = None):
         L.ouster_hip_ctx_set_tuning_cache.argtypes = [vp, C.c_char_p]
         L.ouster_hip_last_decode_tuner.restype = C.c_char_p
         L.ouster_hip_last_decode_tuner.argtypes = [vp]
+    if hasattr(L, "ouster_hip_image_apply"):   # absent only in older A/B builds loaded via OUSTER_HIP_SO
+        u32 = C.c_uint32
+        L.ouster_hip_image_dark_rows.argtypes = [vp, vp, C.c_int, C.c_int, u32, u32, u32, C.c_size_t, vp, vp]
+        L.ouster_hip_image_percentiles.argtypes = [vp, vp, C.c_int, C.c_int, u32, u32, u32, C.c_size_t, vp, C.c_double,
+                                                   C.c_double, vp, vp]
+        L.ouster_hip_image_apply.argtypes = [vp, vp, C.c_int, vp, C.c_int, u32, u32, u32, C.c_size_t, C.c_size_t, vp, vp]
+        L.ouster_hip_image_dark_rows_host.argtypes = [vp, vp, C.c_int, u32, u32, vp, vp]
+        L.ouster_hip_image_percentiles_host.argtypes = [vp, vp, C.c_int, u32, u32, vp, C.c_double, C.c_double, vp, vp]
+        L.ouster_hip_image_apply_host.argtypes = [vp, vp, C.c_int, u32, u32, vp, vp]
     if private_path is None:
         _hip = L
     return L

@@ -25,6 +25,7 @@ DeviceFrameBatch::DeviceFrameBatch(const std::vector<SensorInfo>& sensors, uint3
     if (n_frames == 0) throw std::invalid_argument("DeviceFrameBatch: n_frames must be > 0");
     if (!opt_.tuning_cache.empty()) check(ouster_hip_ctx_set_tuning_cache(ctx_->handle(), opt_.tuning_cache.c_str()));
     const SensorInfo& s0 = sensors[0];
+    n_sensors_ = static_cast<uint32_t>(sensors.size());
     h_ = s0.format.pixels_per_column;
     w_ = s0.format.columns_per_frame;
     for (const auto& s : sensors)
@@ -423,6 +424,48 @@ void DeviceFrameBatch::download_headers(uint32_t frame, uint64_t* ts, uint16_t* 
     if (ts) d_ts_.download(ts, static_cast<size_t>(w_) * 8, static_cast<size_t>(frame) * w_ * 8);
     if (mid) d_mid_.download(mid, static_cast<size_t>(w_) * 2, static_cast<size_t>(frame) * w_ * 2);
     if (st) d_status_.download(st, static_cast<size_t>(w_) * 4, static_cast<size_t>(frame) * w_ * 4);
+}
+
+void* DeviceFrameBatch::render_images(const std::string& field, ImagePipeline& pipe, bool update_state) {
+    ScopedContext on_my_context(ctx_);
+    const auto it = d_dst_.find(field);
+    if (it == d_dst_.end())
+        throw std::invalid_argument("DeviceFrameBatch::render_images: the destaggered plane of '" + field +
+                                    "' was not requested in BatchOptions::destagger");
+    if (pipe.auto_exposure.size() != n_sensors_ || (!pipe.beam_uniformity.empty() && pipe.beam_uniformity.size() != n_sensors_))
+        throw std::invalid_argument("DeviceFrameBatch::render_images: the pipeline needs one object per sensor");
+    const size_t npx = static_cast<size_t>(h_) * w_, es = plane_bytes_per_frame(field) / npx;
+    ChanFieldType type;
+    switch (es) {
+        case 1: type = ChanFieldType::UINT8; break;
+        case 2: type = ChanFieldType::UINT16; break;
+        case 4: type = ChanFieldType::UINT32; break;
+        default: throw std::invalid_argument("DeviceFrameBatch::render_images: '" + field + "' is not an 8, 16 or 32 bit plane");
+    }
+    DeviceBuffer& img = d_images_[field];
+    if (img.size() != npx * 4 * n_frames_) img.resize(npx * 4 * n_frames_);
+    const size_t stride = npx * n_sensors_;   // a sensor's frames are n_sensors_ images apart
+    for (uint32_t s = 0; s < n_sensors_ && s < n_frames_; ++s) {
+        const uint32_t cnt = (n_frames_ - s + n_sensors_ - 1) / n_sensors_;
+        const uint8_t* in = static_cast<const uint8_t*>(it->second.data()) + s * npx * es;
+        float* out = static_cast<float*>(img.data()) + s * npx;
+        if (pipe.beam_uniformity.empty())
+            pipe.auto_exposure[s].update_batch<float>(*ctx_, in, type, cnt, h_, w_, out, update_state, stride, stride);
+        else
+            pipe.beam_uniformity[s].update_batch<float>(*ctx_, in, type, cnt, h_, w_, out, update_state, &pipe.auto_exposure[s],
+                                                        stride, stride);
+    }
+    return img.data();
+}
+
+void DeviceFrameBatch::download_image(const std::string& field, uint32_t frame, float* host) {
+    ScopedContext on_my_context(ctx_);
+    if (frame >= n_frames_) throw std::out_of_range("DeviceFrameBatch: frame index");
+    const auto it = d_images_.find(field);
+    if (it == d_images_.end()) throw std::invalid_argument("DeviceFrameBatch::download_image: render_images('" + field + "') first");
+    const size_t bytes = static_cast<size_t>(h_) * w_ * 4;
+    sync();
+    it->second.download(host, bytes, bytes * frame);
 }
 
 void DeviceFrameBatch::upload_poses(uint32_t frame, const double* poses) {

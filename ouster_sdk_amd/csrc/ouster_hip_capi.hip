@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "host_pool.h"
+#include "k_image.h"
 #include "ouster_hip_dev.h"
 
 using namespace ouster_hip_dev;
@@ -91,6 +92,7 @@ struct ouster_hip_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     DevBuf state, tile_valid, offsets, luts, counts, scratch, slotmap, hdrw, osf_pixels;
+    DevBuf image_mask;                   // ouster_hip_image_dark_rows: the column masks of a batch
     DevBuf user_scratch[8];              // ouster_hip_ctx_scratch: what the *_host calls and bindings stage through
     uint32_t resident_wgs = 512;         // 2 workgroups (80 KB LDS each) per CU
     uint32_t cus = 256;                  // compute units (k_decode_stream: one persistent workgroup each)
@@ -317,6 +319,7 @@ void ouster_hip_ctx_destroy(ouster_hip_ctx* c) {
     c->slotmap.release();
     c->hdrw.release();
     c->osf_pixels.release();
+    c->image_mask.release();
     for (auto& b : c->user_scratch) b.release();
     for (auto& p : c->ev_pool) {
         (void)hipEventDestroy(p.first);
@@ -1239,6 +1242,175 @@ int ouster_hip_dewarp_host(ouster_hip_ctx* ctx, const void* points, const double
     rc = ouster_hip_dewarp(ctx, in.dev, (const double*)po.dev, out.dev, dtype, h, w, 1);
     if (rc != OUSTER_HIP_OK) return rc;
     return host_finish(ctx, out);
+}
+
+// ---- display images (k_image.hip) ----------------------------------------------------------------
+namespace {
+size_t image_elem(int t) {
+    switch (t) {
+        case OUSTER_HIP_U8: return 1;
+        case OUSTER_HIP_U16: return 2;
+        case OUSTER_HIP_U32: case OUSTER_HIP_F32: return 4;
+        case OUSTER_HIP_F64: return 8;
+        default: return 0;
+    }
+}
+// shared argument checks; fills what every image kernel needs.  Returns 1 when there is nothing to do.
+int image_args(ouster_hip_ctx* ctx, const void* planes, int in_type, int out_type, uint32_t n_images, uint32_t h, uint32_t w,
+               size_t image_stride, ImageArgs& a) {
+    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (out_type != OUSTER_HIP_F32 && out_type != OUSTER_HIP_F64)
+        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "out_type must be F32 or F64");
+    if (in_type != OUSTER_HIP_U8 && in_type != OUSTER_HIP_U16 && in_type != OUSTER_HIP_U32 && in_type != out_type)
+        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "in_type must be U8, U16, U32 or out_type");
+    if (n_images == 0 || h == 0 || w == 0) return 1;
+    if (n_images > 65535u) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at most 65535 images per call");
+    if ((uint64_t)h * w > (1ull << 31)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "image larger than 2^31 elements");
+    if (!planes) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL image pointer");
+    if (image_stride && image_stride < (size_t)h * w) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "image_stride smaller than an image");
+    a = ImageArgs{};
+    a.in = planes;
+    a.in_stride = image_stride ? image_stride : (size_t)h * w;
+    a.n_images = n_images;
+    a.h = h;
+    a.w = w;
+    const size_t vb = std::min<size_t>(16, 4 * image_elem(in_type));
+    a.vec = ((uintptr_t)planes % vb == 0) && (a.in_stride % 4 == 0 || n_images == 1);
+    return OUSTER_HIP_OK;
+}
+}  // namespace
+
+int ouster_hip_image_dark_rows(ouster_hip_ctx* ctx, const void* planes, int in_type, int out_type, uint32_t n_images,
+                               uint32_t h, uint32_t w, size_t image_stride, void* medians, uint32_t* n_cols) {
+    ImageArgs a;
+    const int rc = image_args(ctx, planes, in_type, out_type, n_images, h, w, image_stride, a);
+    if (rc) return rc > 0 ? OUSTER_HIP_OK : rc;
+    if (w > IMAGE_MAX_W_DARK) return fail(OUSTER_HIP_ERR_UNSUPPORTED, "dark rows: images wider than %u columns", IMAGE_MAX_W_DARK);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (h < 2) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dark rows need at least two rows");
+    if (!medians) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "medians is NULL");
+    const size_t words = (w + 63) / 64;
+    if (ctx->image_mask.ensure((size_t)n_images * words * 8)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (column masks)");
+    a.col_mask = (uint64_t*)ctx->image_mask.p;
+    a.medians = medians;
+    a.n_cols = n_cols;
+    a.vec = a.vec && (w % 4 == 0);
+    HIP_TRY(launch_image_dark_rows(a, in_type, out_type, ctx->stream));
+    return OUSTER_HIP_OK;
+}
+
+int ouster_hip_image_percentiles(ouster_hip_ctx* ctx, const void* planes, int in_type, int out_type, uint32_t n_images,
+                                 uint32_t h, uint32_t w, size_t image_stride, const void* dark, double lo_percentile,
+                                 double hi_percentile, uint32_t* n, void* lo_hi) {
+    ImageArgs a;
+    const int rc = image_args(ctx, planes, in_type, out_type, n_images, h, w, image_stride, a);
+    if (rc) return rc > 0 ? OUSTER_HIP_OK : rc;
+    if (!n || !lo_hi) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL output pointer");
+    if (!(lo_percentile >= 0) || !(hi_percentile >= 0) || !(lo_percentile + hi_percentile < 1))
+        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "percentiles must be >= 0 and sum to less than 1");
+    HIP_TRY(hipSetDevice(ctx->device));
+    a.dark = dark;
+    a.lo_percentile = lo_percentile;
+    a.hi_percentile = hi_percentile;
+    a.n_positive = n;
+    a.lo_hi = lo_hi;
+    HIP_TRY(launch_image_percentiles(a, in_type, out_type, ctx->stream));
+    return OUSTER_HIP_OK;
+}
+
+int ouster_hip_image_apply(ouster_hip_ctx* ctx, const void* planes, int in_type, void* out, int out_type, uint32_t n_images,
+                           uint32_t h, uint32_t w, size_t in_stride, size_t out_stride, const void* dark,
+                           const ouster_hip_image_map* maps) {
+    ImageArgs a;
+    const int rc = image_args(ctx, planes, in_type, out_type, n_images, h, w, in_stride, a);
+    if (rc) return rc > 0 ? OUSTER_HIP_OK : rc;
+    if (!out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (out_stride && out_stride < (size_t)h * w) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "out_stride smaller than an image");
+    if (out == planes && (in_type != out_type || (out_stride ? out_stride : (size_t)h * w) != a.in_stride))
+        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "in place needs equal types and strides");
+    HIP_TRY(hipSetDevice(ctx->device));
+    a.out = out;
+    a.out_stride = out_stride ? out_stride : (size_t)h * w;
+    a.vec = a.vec && ((uintptr_t)out % 16 == 0) && (a.out_stride % 4 == 0 || n_images == 1);
+    a.dark = dark;
+    a.maps = maps;
+    HIP_TRY(launch_image_apply(a, in_type, out_type, ctx->stream));
+    return OUSTER_HIP_OK;
+}
+
+// One host image: scratch slot 0 holds a foreign image, slot 2 the few numbers that go out, slot 3 those that come in.
+int ouster_hip_image_dark_rows_host(ouster_hip_ctx* ctx, const void* image, int dtype, uint32_t h, uint32_t w, void* medians,
+                                    uint32_t* n_cols) {
+    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    const size_t es = (dtype == OUSTER_HIP_F32 || dtype == OUSTER_HIP_F64) ? image_elem(dtype) : 0;
+    if (!es) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
+    if (h < 2 || w == 0) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dark rows need at least two rows");
+    if (!image || !medians || !n_cols) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HostArg in;
+    int rc = host_arg(ctx, image, (size_t)h * w * es, 0, true, in);
+    if (rc != OUSTER_HIP_OK) return rc;
+    const size_t mbytes = (size_t)(h - 1) * es;
+    if (ctx->user_scratch[2].ensure(mbytes + 8)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (scratch)");
+    uint8_t* d = (uint8_t*)ctx->user_scratch[2].p;
+    rc = ouster_hip_image_dark_rows(ctx, in.dev, dtype, dtype, 1, h, w, 0, d + 8, (uint32_t*)d);
+    if (rc != OUSTER_HIP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(medians, d + 8, mbytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(n_cols, d, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return OUSTER_HIP_OK;
+}
+
+int ouster_hip_image_percentiles_host(ouster_hip_ctx* ctx, const void* image, int dtype, uint32_t h, uint32_t w,
+                                      const void* dark, double lo_percentile, double hi_percentile, uint32_t* n,
+                                      void* lo_hi) {
+    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    const size_t es = (dtype == OUSTER_HIP_F32 || dtype == OUSTER_HIP_F64) ? image_elem(dtype) : 0;
+    if (!es) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
+    if (!image || !n || !lo_hi || h == 0 || w == 0) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "bad image arguments");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HostArg in;
+    int rc = host_arg(ctx, image, (size_t)h * w * es, 0, true, in);
+    if (rc != OUSTER_HIP_OK) return rc;
+    if (ctx->user_scratch[2].ensure(8 + 2 * es)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (scratch)");
+    uint8_t* d = (uint8_t*)ctx->user_scratch[2].p;
+    void* d_dark = nullptr;
+    if (dark) {
+        if (ctx->user_scratch[3].ensure((size_t)h * es)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (scratch)");
+        d_dark = ctx->user_scratch[3].p;
+        HIP_TRY(hipMemcpyAsync(d_dark, dark, (size_t)h * es, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = ouster_hip_image_percentiles(ctx, in.dev, dtype, dtype, 1, h, w, 0, d_dark, lo_percentile, hi_percentile, (uint32_t*)d, d + 8);
+    if (rc != OUSTER_HIP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(n, d, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(lo_hi, d + 8, 2 * es, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return OUSTER_HIP_OK;
+}
+
+int ouster_hip_image_apply_host(ouster_hip_ctx* ctx, void* image, int dtype, uint32_t h, uint32_t w, const void* dark,
+                                const ouster_hip_image_map* map) {
+    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    const size_t es = (dtype == OUSTER_HIP_F32 || dtype == OUSTER_HIP_F64) ? image_elem(dtype) : 0;
+    if (!es) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
+    if (h == 0 || w == 0) return OUSTER_HIP_OK;
+    if (!image) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL image pointer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HostArg io;
+    int rc = host_arg(ctx, image, (size_t)h * w * es, 0, true, io);
+    if (rc != OUSTER_HIP_OK) return rc;
+    const size_t dbytes = dark ? (size_t)h * es : 0, doff = sizeof(ouster_hip_image_map);
+    if (ctx->user_scratch[3].ensure(doff + dbytes)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (scratch)");
+    uint8_t* d = (uint8_t*)ctx->user_scratch[3].p;
+    ouster_hip_image_map m{};
+    if (map) m = *map;
+    else m.use_dark = 1;
+    HIP_TRY(hipMemcpyAsync(d, &m, sizeof m, hipMemcpyHostToDevice, ctx->stream));   // pageable source: staged before the call returns
+    if (dark) HIP_TRY(hipMemcpyAsync(d + doff, dark, dbytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = ouster_hip_image_apply(ctx, io.dev, dtype, io.dev, dtype, 1, h, w, 0, 0, dark ? d + doff : nullptr,
+                                (const ouster_hip_image_map*)d);
+    if (rc != OUSTER_HIP_OK) return rc;
+    return host_finish(ctx, io);
 }
 
 // ---- range-gated, compacting frame dewarp ------------------------------------------------------

@@ -15,6 +15,7 @@
 
 #include <pybind11/functional.h>
 
+#include "ouster/core/image_processing.h"
 #include "ouster/core/lidar_scan.h"
 #include "ouster/hip/frame_stream.h"
 #include "ouster/osf/osf.h"
@@ -771,6 +772,99 @@ PYBIND11_MODULE(core, m) {
             return py::make_tuple(p, c, t);
         },
         py::arg("frame"), py::arg("xyzlut"), py::arg("min_range"), py::arg("max_range"));
+
+    // AutoExposure / BeamUniformityCorrector (python/src/cpp/client/processing.cpp of the reference): update() works in place on
+    // C-contiguous 2-D float32 / float64 arrays and converts nothing -- any other array is a TypeError (py::arg().noconvert()).
+    // A failed GPU call surfaces as ouster_sdk_amd._capi.OusterHipError (a RuntimeError), like the ctypes layer's.
+    {
+        namespace oi = ouster::sdk::core::image;
+        auto guarded = [](auto&& f) {
+            try {
+                f();
+            } catch (const std::invalid_argument&) {
+                throw;
+            } catch (const std::runtime_error& e) {
+                py::object cls = py::module_::import("ouster_sdk_amd._capi").attr("OusterHipError");
+                PyErr_SetString(cls.ptr(), e.what());
+                throw py::error_already_set();
+            }
+        };
+        auto bind_update = [guarded](auto& cls) {
+            using C = typename std::remove_reference<decltype(cls)>::type::type;
+            cls.def(
+                   "update",
+                   [guarded](C& self, py::array_t<float, py::array::c_style> image, bool update_state) {
+                       if (image.ndim() != 2) throw py::type_error("update: expected a 2-D image");
+                       ImgRef<float> ref(image.mutable_data(), static_cast<size_t>(image.shape(0)), static_cast<size_t>(image.shape(1)));
+                       guarded([&] { self.update(ref, update_state); });
+                   },
+                   py::arg("image").noconvert(), py::arg("update_state") = true)
+                .def(
+                    "update",
+                    [guarded](C& self, py::array_t<double, py::array::c_style> image, bool update_state) {
+                        if (image.ndim() != 2) throw py::type_error("update: expected a 2-D image");
+                        ImgRef<double> ref(image.mutable_data(), static_cast<size_t>(image.shape(0)), static_cast<size_t>(image.shape(1)));
+                        guarded([&] { self.update(ref, update_state); });
+                    },
+                    py::arg("image").noconvert(), py::arg("update_state") = true);
+        };
+        // extension: update_batch on a host stack (n, h, w) of uint8 / uint16 / uint32 planes or images of the output type -- staged
+        // to the device, run through the batched kernels (one launch each), returned as a new float32 / float64 stack
+        auto run_batch = [guarded](auto& self, const py::array& planes_in, bool f64, bool update_state, oi::AutoExposure* then) -> py::array {
+            namespace oh = ouster::sdk::hip;
+            using C = typename std::remove_reference<decltype(self)>::type;
+            py::array planes = py::array::ensure(planes_in, py::array::c_style);
+            if (!planes || planes.ndim() != 3) throw py::type_error("update_batch: expected a C-contiguous (n, h, w) array");
+            const char kind = planes.dtype().kind();
+            const py::ssize_t isz = planes.itemsize();
+            ChanFieldType t;
+            if (kind == 'u' && isz == 1) t = ChanFieldType::UINT8;
+            else if (kind == 'u' && isz == 2) t = ChanFieldType::UINT16;
+            else if (kind == 'u' && isz == 4) t = ChanFieldType::UINT32;
+            else if (kind == 'f' && isz == (f64 ? 8 : 4)) t = f64 ? ChanFieldType::FLOAT64 : ChanFieldType::FLOAT32;
+            else throw py::type_error("update_batch: planes must be uint8 / uint16 / uint32 or of the output dtype");
+            const std::vector<py::ssize_t> shape = {planes.shape(0), planes.shape(1), planes.shape(2)};
+            const uint32_t n = static_cast<uint32_t>(shape[0]), h = static_cast<uint32_t>(shape[1]), w = static_cast<uint32_t>(shape[2]);
+            py::array out = f64 ? py::array(py::array_t<double>(shape)) : py::array(py::array_t<float>(shape));
+            if (planes.size() == 0) return out;
+            guarded([&] {
+                std::shared_ptr<oh::Context> ctx = oh::Context::current();
+                oh::ScopedContext on_ctx(ctx);
+                oh::DeviceBuffer din(static_cast<size_t>(planes.nbytes())), dout(static_cast<size_t>(out.nbytes()));
+                din.upload(planes.data(), static_cast<size_t>(planes.nbytes()));
+                auto call = [&](auto* o) {
+                    if constexpr (std::is_same<C, oi::AutoExposure>::value) self.update_batch(*ctx, din.data(), t, n, h, w, o, update_state);
+                    else self.update_batch(*ctx, din.data(), t, n, h, w, o, update_state, then);
+                };
+                if (f64) call(static_cast<double*>(dout.data()));
+                else call(static_cast<float*>(dout.data()));
+                dout.download(out.mutable_data(), static_cast<size_t>(out.nbytes()));
+            });
+            return out;
+        };
+        py::class_<oi::AutoExposure> ae(m, "AutoExposure");
+        ae.def(py::init<>())
+            .def(py::init<int>(), py::arg("update_every"))
+            .def(py::init<double, double, int, double>(), py::arg("lo_percentile"), py::arg("hi_percentile"),
+                 py::arg("update_every"), py::arg("damping") = 0.9)
+            .def_property_readonly("lo_state", &oi::AutoExposure::lo_state)   // extensions: the state, read-only
+            .def_property_readonly("hi_state", &oi::AutoExposure::hi_state)
+            .def_property_readonly("initialized", &oi::AutoExposure::initialized);
+        bind_update(ae);
+        ae.def("update_batch", [run_batch](oi::AutoExposure& self, const py::array& planes, bool float64, bool update_state) {
+            return run_batch(self, planes, float64, update_state, nullptr);
+        }, py::arg("planes"), py::arg("float64") = false, py::arg("update_state") = true);
+        py::class_<oi::BeamUniformityCorrector> buc(m, "BeamUniformityCorrector");
+        buc.def(py::init<>()).def_property_readonly("dark_count", [](const oi::BeamUniformityCorrector& b) {
+            py::array_t<double> a(static_cast<py::ssize_t>(b.dark_count().size()));
+            if (!b.dark_count().empty()) std::memcpy(a.mutable_data(), b.dark_count().data(), b.dark_count().size() * 8);
+            return a;
+        });
+        bind_update(buc);
+        buc.def("update_batch", [run_batch](oi::BeamUniformityCorrector& self, const py::array& planes, bool float64, bool update_state,
+                                            oi::AutoExposure* then) { return run_batch(self, planes, float64, update_state, then); },
+                py::arg("planes"), py::arg("float64") = false, py::arg("update_state") = true, py::arg("then") = nullptr);
+    }
 
     // streaming pipeline for host-side packets (include/ouster/hip/frame_stream.h; extension over the
     // reference's Python surface).  The callback receives a dict of numpy VIEWS of pinned memory that

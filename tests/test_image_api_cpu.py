@@ -1,0 +1,75 @@
+"""The public surface of the display-image feature, checked without a GPU: C ABI symbols, the ouster.sdk.core names, constructor
+shapes, the TypeError on a wrong dtype, the loud failure without a GPU (no CPU fallback) and a C++ caller that compiles and
+links against include/ouster/core/image_processing.h."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, has_gpu
+from ouster_sdk_amd import _capi as capi
+
+sys.path.insert(0, os.path.join(ROOT, "ouster_sdk_amd", "compat"))
+
+IMAGE_SYMBOLS = ["ouster_hip_image_dark_rows", "ouster_hip_image_percentiles", "ouster_hip_image_apply",
+                 "ouster_hip_image_dark_rows_host", "ouster_hip_image_percentiles_host", "ouster_hip_image_apply_host"]
+
+
+def test_image_symbols_are_exported():
+    L = capi.load_hip()
+    for name in IMAGE_SYMBOLS:
+        assert name in capi.ABI_SYMBOLS and hasattr(L, name), name
+    import ctypes as C
+    assert C.sizeof(capi.ImageMap) == 32
+
+
+def test_compat_names_and_constructors():
+    from ouster.sdk.core import AutoExposure, BeamUniformityCorrector
+    import ouster_sdk_amd.core as core
+    assert AutoExposure is core.AutoExposure and BeamUniformityCorrector is core.BeamUniformityCorrector
+    AutoExposure()
+    AutoExposure(5)
+    AutoExposure(0.05, 0.2, 2)
+    AutoExposure(0.05, 0.2, 2, 0.5)
+    AutoExposure(lo_percentile=0.05, hi_percentile=0.2, update_every=2, damping=0.5)
+    BeamUniformityCorrector()
+    for obj in (AutoExposure(), BeamUniformityCorrector()):
+        with pytest.raises(TypeError):
+            obj.update(np.ones((8, 8), np.uint16))
+        with pytest.raises(TypeError):
+            obj.update(np.ones((8, 8), np.float32).T.copy().T)      # not C-contiguous: nothing is converted
+        with pytest.raises(TypeError):
+            obj.update(np.ones(8, np.float32))
+
+
+@pytest.mark.skipif(has_gpu(), reason="checks the no-GPU failure mode")
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_update_without_a_gpu_raises_and_leaves_the_image(dtype):
+    from ouster.sdk.core import AutoExposure, BeamUniformityCorrector
+    img = np.arange(1, 64 * 32 + 1, dtype=dtype).reshape(64, 32)
+    keep = img.copy()
+    for obj in (AutoExposure(), BeamUniformityCorrector()):
+        with pytest.raises(capi.OusterHipError):
+            obj.update(img)
+        assert np.array_equal(img, keep)
+
+
+def test_cpp_caller_compiles_links_and_runs():
+    """The flags of tests/cpp/Makefile (the build of the other C++ tests), on tests/cpp/image_processing_snippet.cpp."""
+    rocm = os.environ.get("ROCM", "/opt/rocm")
+    out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "image_processing_snippet")
+    lib = os.path.join(ROOT, "ouster_sdk_amd", "lib")
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
+                           "-I" + os.path.join(ROOT, "include"), "-o", exe,
+                           os.path.join(ROOT, "tests", "cpp", "image_processing_snippet.cpp"),
+                           "-L" + lib, "-louster_core_amd", "-louster_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
+                           "-Wl,-rpath," + lib, "-Wl,-rpath," + os.path.join(rocm, "lib")])
+    env = dict(os.environ)
+    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
+    p = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert p.stdout.startswith("ok" if has_gpu() else "no-gpu"), p.stdout
