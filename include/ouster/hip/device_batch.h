@@ -177,6 +177,34 @@ class DeviceFrameBatch {
     /** One frame's image of the last render_images(field, ...) (h * w floats; synchronous). */
     void download_image(const std::string& field, uint32_t frame, float* host);
 
+    /** frame_ops on the resident batch (core/frame_ops.h; csrc/k_frame_ops.hip): asynchronous on the batch's stream, the whole
+     *  batch in one launch (clip and a filter_xyz whose fields follow both clouds: two).  Fields: nullptr (clip / mask: an empty list) = every
+     *  staggered plane the batch holds; a listed name the batch does not hold is skipped, as the reference skips a field a
+     *  frame lacks (a batch holds pixel planes only).  Every op keeps the batch consistent:
+     *   - the destaggered copy (BatchOptions::destagger) of a target gets the same pixels invalidated.  The batch destaggers every
+     *     frame with the FIRST sensor's pixel_shift_by_row (as decode() does); filter_uv "v" is defined on that image;
+     *   - RANGE / RANGE2 as a target of a batch with XYZ: the invalidated pixels' points become what projection gives for the
+     *     new range.  Implemented for invalid == 0 (the point (0, 0, 0): the cloud equals ouster_hip_cartesian of the filtered
+     *     plane bit for bit) in the sensor / body frame; invalid != 0, or a world-frame cloud (xyz_world_frame), throws
+     *     std::invalid_argument;
+     *   - the per-column gate counts dewarp() reuses are dropped whenever RANGE is modified.
+     *  `invalid` is checked against every target's type before anything is launched.
+     *  @throw std::invalid_argument with the reference's messages for bad bounds / coord_2d / mask shapes */
+    void clip(const std::vector<std::string>& fields, double lower, double upper, double invalid = 0);
+    /** @throw std::out_of_range if the batch does not hold the staggered plane of `field` */
+    void filter_field(const std::string& field, double lower, double upper, double invalid = 0,
+                      const std::vector<std::string>* filtered_fields = nullptr);
+    void filter_uv(const std::string& coord_2d, size_t lower, size_t upper, double invalid = 0,
+                   const std::vector<std::string>* filtered_fields = nullptr);
+    /** One (h, w) mask per sensor (host memory; copied before the call returns); frame f uses masks[f % sensors].
+     *  @throw std::invalid_argument when the count is not the sensor count or a mask has another shape */
+    void mask(const std::vector<std::string>& fields, const std::vector<core::ImgRef<const uint8_t>>& masks);
+    /** Pixels whose `axis` coordinate in the batch's OWN cloud (the stored value, cast to double) lies inside [lower, upper]
+     *  are invalidated; second-return fields follow RANGE2's cloud where the batch has one, the others RANGE's.  Needs
+     *  BatchOptions::xyz; world_frame must equal BatchOptions::xyz_world_frame (@throw std::invalid_argument otherwise). */
+    void filter_xyz(int axis, double lower, double upper, double invalid = 0,
+                    const std::vector<std::string>* filtered_fields = nullptr, bool world_frame = false);
+
     /** Per-column body_to_world poses of one frame (w x 16 doubles, row-major 4x4 each; identity
      *  until set), the input of dewarp(). */
     void upload_poses(uint32_t frame, const double* poses_w_by_16);
@@ -201,6 +229,10 @@ class DeviceFrameBatch {
     void download_dewarped(void* points, uint32_t* frame_idxs, uint32_t* col_idxs, uint64_t* timestamps_ns);
 
    private:
+    struct FopsTargets;
+    void fops_targets_(const std::vector<std::string>* fields, double invalid, FopsTargets& out);
+    void fops_invalidate_(const void* pred, FopsTargets& t);
+    DeviceBuffer d_masks_;   // mask(): u8 [sensors][h][w]
     std::shared_ptr<Context> ctx_;
     core::PacketFormat pf_;
     uint32_t n_frames_, h_, w_, slots_;

@@ -46,6 +46,10 @@ extern "C" {
 #define OUSTER_HIP_U16 2
 #define OUSTER_HIP_U32 3
 #define OUSTER_HIP_U64 4
+#define OUSTER_HIP_I8 5
+#define OUSTER_HIP_I16 6
+#define OUSTER_HIP_I32 7
+#define OUSTER_HIP_I64 8
 #define OUSTER_HIP_F32 9
 #define OUSTER_HIP_F64 10
 #define OUSTER_HIP_F16 12
@@ -481,6 +485,78 @@ int ouster_hip_image_percentiles_host(ouster_hip_ctx* ctx, const void* image, in
                                       void* lo_hi);
 int ouster_hip_image_apply_host(ouster_hip_ctx* ctx, void* image, int dtype, uint32_t h, uint32_t w, const void* dark,
                                 const ouster_hip_image_map* map);
+
+/* ---- frame_ops: clip / filter / mask / beam selection ------------------------------------------------ */
+/* The device half of ouster::sdk::core::frame_ops (ouster_core/include/ouster/core/frame_ops.h, src/frame_ops.cpp), batched:
+ * n_images images of h x w pixels per plane, and a LIST of planes of mixed element types per call (one launch for up to 32
+ * planes).  Element types: U8 / U16 / U32 / U64, I8 / I16 / I32 / I64, F32, F64 -- what impl::visit_field_2d visits.
+ * n_images <= 65535, h * w <= 2^31; every plane pointer is aligned to its element size.
+ *
+ * `invalid` is converted like static_cast<T>(invalid) where that is defined: truncated toward zero for an integer type.  A
+ * value that does not fit the plane's type after truncation, NaN for an integer type, or a finite value beyond FLT_MAX for
+ * F32 (all undefined in the reference) is INVALID_ARGUMENT, and it is checked for EVERY plane before anything is written. */
+/* ouster_hip_frame_ops_invalidate only: the plane is a cloud [n_images][h * w][3] of float / double (image_stride in points).
+ * The point of an invalidated pixel becomes (0, 0, 0) -- what projection gives for range 0, so a cloud stays
+ * ouster_hip_cartesian of its range plane when that plane is invalidated to 0 in the same call.  `invalid` must be 0, no twin. */
+#define OUSTER_HIP_FOPS_XYZ_F32 100
+#define OUSTER_HIP_FOPS_XYZ_F64 101
+typedef struct ouster_hip_fops_plane {
+    void* data;           /* image i at data + i * image_stride elements */
+    void* twin;           /* invalidate only, nullable: the destaggered copy of the same images (same type and stride); the
+                             pixel invalidated at (r, c) is invalidated there at (r, (c + shift[r]) mod w).  Needs pred->shifts */
+    size_t image_stride;  /* elements between images; 0: dense (h * w) */
+    int32_t type;         /* OUSTER_HIP_U8 ... OUSTER_HIP_F64, or OUSTER_HIP_FOPS_XYZ_* */
+    int32_t reserved;
+    double invalid;       /* this plane's replacement value */
+} ouster_hip_fops_plane;
+
+/* Which pixels ouster_hip_frame_ops_invalidate invalidates.  Evaluated once per pixel, for all planes. */
+#define OUSTER_HIP_FOPS_PRED_KEY 1   /* lower <= double(key(r, c)) <= upper: filter_field (BuildFilterMaskOp); a NaN key is kept */
+#define OUSTER_HIP_FOPS_PRED_ROWS 2  /* lo <= r < hi: filter_uv "u" */
+#define OUSTER_HIP_FOPS_PRED_COLS 3  /* lo <= (c + shift[r]) mod w < hi: filter_uv "v", evaluated on the staggered image */
+#define OUSTER_HIP_FOPS_PRED_MASK 4  /* mask(r, c) == 0: mask (ApplyMaskOp); image i uses masks[i % n_masks] */
+#define OUSTER_HIP_FOPS_PRED_XYZ 5   /* lower <= double(xyz(r * w + c)[axis]) <= upper: filter_xyz */
+typedef struct ouster_hip_fops_pred {
+    int32_t kind;          /* OUSTER_HIP_FOPS_PRED_* */
+    int32_t src_type;      /* KEY: element type of the key plane; XYZ: OUSTER_HIP_F32 or OUSTER_HIP_F64 */
+    const void* src;       /* KEY: [n_images] key planes (may be one of the targets); MASK: [n_masks] u8 masks;
+                              XYZ: [n_images][h * w][3] points */
+    size_t src_stride;     /* elements (XYZ: points) between images / masks; 0: dense (h * w) */
+    uint32_t n_masks;      /* MASK */
+    uint32_t axis;         /* XYZ: 0, 1, 2 */
+    double lower, upper;   /* KEY / XYZ: value range, inclusive; +-inf allowed */
+    uint32_t lo, hi;       /* ROWS / COLS: index range [lo, hi); lo <= hi <= h (ROWS) or w (COLS) */
+    const int32_t* shifts; /* HOST [n_shift_tables][h] pixel_shift_by_row tables (any integers): COLS, and every plane with a twin */
+    uint32_t n_shift_tables; /* image i uses table i % n_shift_tables (multi-sensor batches interleave sensors) */
+    uint32_t reserved;
+} ouster_hip_fops_pred;
+
+/* static_cast<T>(invalid) as the bit pattern the kernels write (low bytes of *bits), with the checks above.  Needs no GPU. */
+int ouster_hip_frame_ops_invalid_bits(int type, double invalid, uint64_t* bits);
+/* ClipOp (frame_ops.cpp:151-163), in place: a value is kept iff lower <= double(v) <= upper (NaN: replaced; u64 / i64 are
+ * converted with round-to-nearest-even like the host), else it becomes the plane's `invalid`. */
+int ouster_hip_frame_ops_clip(ouster_hip_ctx* ctx, const ouster_hip_fops_plane* planes, uint32_t n_planes,
+                              uint32_t n_images, uint32_t h, uint32_t w, double lower, double upper);
+/* BuildFilterMaskOp + ApplyMaskOp (frame_ops.cpp:165-207) without the mask image in between: the planes are written only where
+ * the predicate holds and are never read (the key plane may be among them: a pixel's predicate is evaluated before its stores). */
+int ouster_hip_frame_ops_invalidate(ouster_hip_ctx* ctx, const ouster_hip_fops_pred* pred,
+                                    const ouster_hip_fops_plane* planes, uint32_t n_planes, uint32_t n_images,
+                                    uint32_t h, uint32_t w);
+/* copy_selected_rows (frame_ops.cpp:134-149): dst[p] [n_images][n_sel][w] = rows indices[] of src[p] [n_images][h][w], elements
+ * of elem_bytes[p] bytes (1, 2, 4, 8).  indices: HOST array, every value < h (else INVALID_ARGUMENT); src and dst must not overlap. */
+int ouster_hip_frame_ops_select_rows(ouster_hip_ctx* ctx, const void* const* src, void* const* dst,
+                                     const uint32_t* elem_bytes, uint32_t n_planes, uint32_t n_images, uint32_t h,
+                                     uint32_t w, const uint32_t* indices, uint32_t n_sel);
+/* The same on ONE host frame (n_images = 1, dense): every data / src pointer is a HOST pointer, the result is in place when the
+ * call returns.  Pool memory (ouster_hip_host_alloc) is worked on where it lies; other memory goes through the context's
+ * grow-only scratch (slot 0: the planes, slot 1: the predicate source / the selected rows).  `twin` must be NULL. */
+int ouster_hip_frame_ops_clip_host(ouster_hip_ctx* ctx, const ouster_hip_fops_plane* planes, uint32_t n_planes, uint32_t h,
+                                   uint32_t w, double lower, double upper);
+int ouster_hip_frame_ops_invalidate_host(ouster_hip_ctx* ctx, const ouster_hip_fops_pred* pred,
+                                         const ouster_hip_fops_plane* planes, uint32_t n_planes, uint32_t h, uint32_t w);
+int ouster_hip_frame_ops_select_rows_host(ouster_hip_ctx* ctx, const void* const* src, void* const* dst,
+                                          const uint32_t* elem_bytes, uint32_t n_planes, uint32_t h, uint32_t w,
+                                          const uint32_t* indices, uint32_t n_sel);
 
 /* ---- instrumentation ------------------------------------------------------ */
 /* Average duration in ms of the dominant decode kernel over the launches made

@@ -19,6 +19,7 @@ CORE_SO = os.path.join(LIB_DIR, "libouster_core_amd.so")
 
 MAX_FIELDS = 32
 U8, U16, U32, U64, F32, F64, F16 = 1, 2, 3, 4, 9, 10, 12
+I8, I16, I32, I64 = 5, 6, 7, 8
 
 OK = 0
 ERR_INVALID_ARGUMENT = -1
@@ -82,6 +83,26 @@ class ImageMap(C.Structure):
 IMAGE_MAP_NONE, IMAGE_MAP_SCALE, IMAGE_MAP_AFFINE = 0, 1, 2
 
 
+class FopsPlane(C.Structure):
+    """ouster_hip_fops_plane (include/ouster_hip.h): one plane of a frame_ops call"""
+    _fields_ = [("data", C.c_void_p), ("twin", C.c_void_p), ("image_stride", C.c_size_t), ("type", C.c_int32),
+                ("reserved", C.c_int32), ("invalid", C.c_double)]
+
+
+class FopsPred(C.Structure):
+    """ouster_hip_fops_pred (include/ouster_hip.h): which pixels ouster_hip_frame_ops_invalidate invalidates"""
+    _fields_ = [("kind", C.c_int32), ("src_type", C.c_int32), ("src", C.c_void_p), ("src_stride", C.c_size_t),
+                ("n_masks", C.c_uint32), ("axis", C.c_uint32), ("lower", C.c_double), ("upper", C.c_double),
+                ("lo", C.c_uint32), ("hi", C.c_uint32), ("shifts", C.c_void_p), ("n_shift_tables", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+FOPS_PRED_KEY, FOPS_PRED_ROWS, FOPS_PRED_COLS, FOPS_PRED_MASK, FOPS_PRED_XYZ = 1, 2, 3, 4, 5
+# numpy dtype name -> element type tag of a frame_ops plane
+FOPS_TYPES = {"uint8": U8, "uint16": U16, "uint32": U32, "uint64": U64, "int8": I8, "int16": I16, "int32": I32,
+              "int64": I64, "float32": F32, "float64": F64}
+
+
 # every symbol include/ouster_hip.h declares (checked by tests/test_abi.py)
 class AllocStats(C.Structure):
     """ouster_hip_alloc_stats (include/ouster_hip.h)"""
@@ -105,6 +126,10 @@ ABI_SYMBOLS = [
     # display images: the device half of BeamUniformityCorrector / AutoExposure
     "ouster_hip_image_dark_rows", "ouster_hip_image_percentiles", "ouster_hip_image_apply",
     "ouster_hip_image_dark_rows_host", "ouster_hip_image_percentiles_host", "ouster_hip_image_apply_host",
+    # frame_ops: clip / filter / mask / beam selection
+    "ouster_hip_frame_ops_invalid_bits", "ouster_hip_frame_ops_clip", "ouster_hip_frame_ops_invalidate",
+    "ouster_hip_frame_ops_select_rows", "ouster_hip_frame_ops_clip_host", "ouster_hip_frame_ops_invalidate_host",
+    "ouster_hip_frame_ops_select_rows_host",
 ]
 
 _hip = None
@@ -207,6 +232,17 @@ def load_hip(private_path: Optional[str] = None):
         L.ouster_hip_image_dark_rows_host.argtypes = [vp, vp, C.c_int, u32, u32, vp, vp]
         L.ouster_hip_image_percentiles_host.argtypes = [vp, vp, C.c_int, u32, u32, vp, C.c_double, C.c_double, vp, vp]
         L.ouster_hip_image_apply_host.argtypes = [vp, vp, C.c_int, u32, u32, vp, vp]
+    if hasattr(L, "ouster_hip_frame_ops_clip"):   # absent only in older A/B builds loaded via OUSTER_HIP_SO
+        u32 = C.c_uint32
+        L.ouster_hip_frame_ops_invalid_bits.argtypes = [C.c_int, C.c_double, C.POINTER(C.c_uint64)]
+        L.ouster_hip_frame_ops_clip.argtypes = [vp, C.POINTER(FopsPlane), u32, u32, u32, u32, C.c_double, C.c_double]
+        L.ouster_hip_frame_ops_invalidate.argtypes = [vp, C.POINTER(FopsPred), C.POINTER(FopsPlane), u32, u32, u32, u32]
+        L.ouster_hip_frame_ops_select_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32), u32, u32, u32, u32,
+                                                       C.POINTER(u32), u32]
+        L.ouster_hip_frame_ops_clip_host.argtypes = [vp, C.POINTER(FopsPlane), u32, u32, u32, C.c_double, C.c_double]
+        L.ouster_hip_frame_ops_invalidate_host.argtypes = [vp, C.POINTER(FopsPred), C.POINTER(FopsPlane), u32, u32, u32]
+        L.ouster_hip_frame_ops_select_rows_host.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32), u32, u32, u32,
+                                                            C.POINTER(u32), u32]
     if private_path is None:
         _hip = L
     return L
@@ -408,3 +444,18 @@ class Lut:
                 self.h = None
         except Exception:
             pass
+
+
+def fops_planes(ptrs: Sequence[int], types: Sequence[int], invalid=0.0, twins: Optional[Sequence[int]] = None,
+                strides: Optional[Sequence[int]] = None):
+    """A ctypes array of ouster_hip_fops_plane from raw pointers (device or host) and element type tags; `invalid` is one
+    value for all planes or one per plane."""
+    n = len(ptrs)
+    arr = (FopsPlane * max(n, 1))()
+    for i in range(n):
+        arr[i].data = ptrs[i]
+        arr[i].twin = twins[i] if twins else None
+        arr[i].image_stride = strides[i] if strides else 0
+        arr[i].type = types[i]
+        arr[i].invalid = float(invalid[i] if isinstance(invalid, (list, tuple)) else invalid)
+    return arr

@@ -191,6 +191,214 @@ void DeviceFrameBatch::decode() {
                             static_cast<uint32_t>(luts.size())));
 }
 
+// ---- frame_ops on the resident batch ------------------------------------------------------------------------------------
+struct DeviceFrameBatch::FopsTargets {
+    std::vector<ouster_hip_fops_plane> planes;   // the staggered planes with their destaggered twins ...
+    std::vector<ouster_hip_fops_plane> clouds;   // ... and the clouds of the range planes among them
+    std::vector<std::string> names;              // planes[i] is the plane of names[i]
+    bool range = false;
+};
+
+void DeviceFrameBatch::fops_targets_(const std::vector<std::string>* fields, double invalid, FopsTargets& out) {
+    std::vector<std::string> names;
+    if (fields) {   // nullptr: every plane (clip / mask hand an empty list over as nullptr, like the reference)
+        names = *fields;
+    } else {
+        for (const auto& f : fields_) names.push_back(f.first);
+    }
+    for (const auto& name : names) {
+        auto p = d_planes_.find(name);
+        if (p == d_planes_.end()) continue;
+        uint32_t es = 0;
+        size_t idx = 0;
+        for (size_t i = 0; i < fields_.size(); ++i)
+            if (fields_[i].first == name) es = fields_[i].second, idx = i;
+        int type = 0;
+        switch (es) {
+            case 1: type = OUSTER_HIP_U8; break;
+            case 2: type = OUSTER_HIP_U16; break;
+            case 4: type = OUSTER_HIP_U32; break;
+            case 8: type = OUSTER_HIP_U64; break;
+            default: continue;   // packed multi-channel planes: not visited, like FLOAT16 in the reference
+        }
+        uint64_t bits;
+        check(ouster_hip_frame_ops_invalid_bits(type, invalid, &bits));
+        ouster_hip_fops_plane pl{};
+        pl.data = p->second.data();
+        auto q = d_dst_.find(name);
+        if (q != d_dst_.end()) pl.twin = q->second.data();
+        pl.type = type;
+        pl.invalid = invalid;
+        out.planes.push_back(pl);
+        out.names.push_back(name);
+        for (int k = 0; k < 2; ++k) {
+            if (xyz_field_[k] != static_cast<int>(idx) || d_xyz_[k].size() == 0) continue;
+            if (invalid != 0)
+                throw std::invalid_argument("DeviceFrameBatch: invalid == " + std::to_string(invalid) + " on " + name +
+                                            " of a batch with XYZ is not supported (only 0 is)");
+            if (opt_.xyz_world_frame)
+                throw std::invalid_argument("DeviceFrameBatch: " + name + " of a batch with world-frame XYZ cannot be a frame_ops target");
+            ouster_hip_fops_plane c{};
+            c.data = d_xyz_[k].data();
+            c.type = opt_.xyz_f64 ? OUSTER_HIP_FOPS_XYZ_F64 : OUSTER_HIP_FOPS_XYZ_F32;
+            out.clouds.push_back(c);
+        }
+        if (name == ChanField::RANGE) out.range = true;
+    }
+}
+
+void DeviceFrameBatch::fops_invalidate_(const void* pred_in, FopsTargets& t) {
+    if (t.planes.empty()) return;
+    ouster_hip_fops_pred pred = *static_cast<const ouster_hip_fops_pred*>(pred_in);
+    bool twins = false;
+    for (const auto& p : t.planes) twins = twins || p.twin != nullptr;
+    if (twins || pred.kind == OUSTER_HIP_FOPS_PRED_COLS) {
+        if (shifts_.size() != h_) throw std::invalid_argument("image height does not match shifts size");
+        pred.shifts = shifts_.data();
+        pred.n_shift_tables = 1;
+    }
+    std::vector<ouster_hip_fops_plane> all = t.planes;
+    all.insert(all.end(), t.clouds.begin(), t.clouds.end());
+    if (t.range) gate_valid_ = false;   // dewarp() counts again
+    check(ouster_hip_frame_ops_invalidate(default_ctx(), &pred, all.data(), static_cast<uint32_t>(all.size()), n_frames_, h_, w_));
+}
+
+void DeviceFrameBatch::clip(const std::vector<std::string>& fields, double lower, double upper, double invalid) {
+    ScopedContext on_my_context(ctx_);
+    FopsTargets t;
+    fops_targets_(fields.empty() ? nullptr : &fields, invalid, t);
+    if (t.planes.empty()) return;
+    // clip is element-wise: the destaggered copy is clipped as a plane of its own, in the same launch
+    std::vector<ouster_hip_fops_plane> all;
+    for (const auto& p : t.planes) {
+        ouster_hip_fops_plane a = p;
+        a.twin = nullptr;
+        all.push_back(a);
+        if (p.twin) {
+            a.data = p.twin;
+            all.push_back(a);
+        }
+    }
+    if (t.range) gate_valid_ = false;
+    check(ouster_hip_frame_ops_clip(default_ctx(), all.data(), static_cast<uint32_t>(all.size()), n_frames_, h_, w_, lower, upper));
+    // invalid is 0 here (fops_targets_): a point whose range is now 0 -- clipped, or 0 before, whose point is (0, 0, 0) already --
+    // becomes (0, 0, 0)
+    size_t c = 0;
+    for (size_t i = 0; i < t.planes.size() && c < t.clouds.size(); ++i) {
+        if (t.names[i] != ChanField::RANGE && t.names[i] != ChanField::RANGE2) continue;
+        ouster_hip_fops_pred pred{};
+        pred.kind = OUSTER_HIP_FOPS_PRED_KEY;
+        pred.src_type = OUSTER_HIP_U32;
+        pred.src = t.planes[i].data;
+        pred.lower = pred.upper = 0.0;
+        check(ouster_hip_frame_ops_invalidate(default_ctx(), &pred, &t.clouds[c++], 1, n_frames_, h_, w_));
+    }
+}
+
+void DeviceFrameBatch::filter_field(const std::string& field, double lower, double upper, double invalid,
+                                    const std::vector<std::string>* filtered_fields) {
+    ScopedContext on_my_context(ctx_);
+    auto key = d_planes_.find(field);
+    if (key == d_planes_.end()) throw std::out_of_range("DeviceFrameBatch: no plane '" + field + "'");
+    ouster_hip_fops_pred pred{};
+    pred.kind = OUSTER_HIP_FOPS_PRED_KEY;
+    switch (plane_bytes_per_frame(field) / (static_cast<size_t>(h_) * w_)) {
+        case 1: pred.src_type = OUSTER_HIP_U8; break;
+        case 2: pred.src_type = OUSTER_HIP_U16; break;
+        case 4: pred.src_type = OUSTER_HIP_U32; break;
+        case 8: pred.src_type = OUSTER_HIP_U64; break;
+        default: throw std::invalid_argument("filter_field requires a pixel field with shape (h, w) to build a mask");
+    }
+    pred.src = key->second.data();
+    pred.lower = lower;
+    pred.upper = upper;
+    FopsTargets t;
+    fops_targets_(filtered_fields, invalid, t);
+    fops_invalidate_(&pred, t);
+}
+
+void DeviceFrameBatch::filter_uv(const std::string& coord_2d, size_t lower, size_t upper, double invalid,
+                                 const std::vector<std::string>* filtered_fields) {
+    ScopedContext on_my_context(ctx_);
+    if (coord_2d != "u" && coord_2d != "v")
+        throw std::invalid_argument("coord_2d == " + coord_2d + " must be either 'u' or 'v'");
+    const size_t coord_size = coord_2d == "u" ? h_ : w_;
+    if (lower > coord_size || upper > coord_size)
+        throw std::invalid_argument("lower == " + std::to_string(lower) + " and upper == " + std::to_string(upper) +
+                                    " must be in the range [0, " + std::to_string(coord_size) + "]");
+    if (lower > upper)
+        throw std::invalid_argument("lower == " + std::to_string(lower) + " must be less than upper == " + std::to_string(upper));
+    ouster_hip_fops_pred pred{};
+    pred.kind = coord_2d == "u" ? OUSTER_HIP_FOPS_PRED_ROWS : OUSTER_HIP_FOPS_PRED_COLS;
+    pred.lo = static_cast<uint32_t>(lower);
+    pred.hi = static_cast<uint32_t>(upper);
+    FopsTargets t;
+    fops_targets_(filtered_fields, invalid, t);
+    fops_invalidate_(&pred, t);
+}
+
+void DeviceFrameBatch::mask(const std::vector<std::string>& fields, const std::vector<ImgRef<const uint8_t>>& masks) {
+    ScopedContext on_my_context(ctx_);
+    if (masks.size() != n_sensors_)
+        throw std::invalid_argument("DeviceFrameBatch::mask needs one mask per sensor: got " + std::to_string(masks.size()) +
+                                    ", the batch has " + std::to_string(n_sensors_));
+    for (const auto& m : masks)
+        if (m.rows() != h_ || m.cols() != w_) throw std::invalid_argument("Used mask size doesn't match frame size");
+    FopsTargets t;
+    fops_targets_(fields.empty() ? nullptr : &fields, 0, t);
+    const size_t npx = static_cast<size_t>(h_) * w_;
+    std::vector<uint8_t> all(npx * n_sensors_);
+    for (size_t s = 0; s < masks.size(); ++s) std::memcpy(all.data() + s * npx, masks[s].data(), npx);
+    sync();   // a mask() still in flight reads the buffer this call is about to overwrite
+    d_masks_.resize(all.size());
+    d_masks_.upload(all.data(), all.size());   // synchronous: `all` may go
+    ouster_hip_fops_pred pred{};
+    pred.kind = OUSTER_HIP_FOPS_PRED_MASK;
+    pred.src = d_masks_.data();
+    pred.n_masks = n_sensors_;
+    fops_invalidate_(&pred, t);
+}
+
+void DeviceFrameBatch::filter_xyz(int axis, double lower, double upper, double invalid,
+                                  const std::vector<std::string>* filtered_fields, bool world_frame) {
+    ScopedContext on_my_context(ctx_);
+    if (axis < 0 || axis > 2) throw std::invalid_argument("axis_idx == " + std::to_string(axis) + " must be in the range [0, 2]");
+    if (!opt_.xyz || (d_xyz_[0].size() == 0 && d_xyz_[1].size() == 0))
+        throw std::invalid_argument("DeviceFrameBatch::filter_xyz needs BatchOptions::xyz");
+    if (world_frame != opt_.xyz_world_frame)
+        throw std::invalid_argument(std::string("DeviceFrameBatch::filter_xyz: world_frame must equal BatchOptions::xyz_world_frame (") +
+                                    (opt_.xyz_world_frame ? "true)" : "false)"));
+    FopsTargets t;
+    fops_targets_(filtered_fields, invalid, t);
+    // which cloud decides for a field (python/src/ouster/sdk/core/frame_ops.py:128-136)
+    FopsTargets group[2];
+    size_t cloud = 0;
+    for (size_t i = 0; i < t.planes.size(); ++i) {
+        const std::string& n = t.names[i];
+        const bool second = n == "RANGE2" || n == "SIGNAL2" || n == "REFLECTIVITY2" || n == "FLAGS2";
+        int k = second ? 1 : 0;
+        if (d_xyz_[k].size() == 0) k = 1 - k;
+        group[k].planes.push_back(t.planes[i]);
+        group[k].names.push_back(n);
+        if (n == ChanField::RANGE) group[k].range = true;
+        if ((n == ChanField::RANGE || n == ChanField::RANGE2) && cloud < t.clouds.size()) group[k].clouds.push_back(t.clouds[cloud++]);
+    }
+    // A launch reads its own cloud before it writes it (per pixel), and never the other launch's: group 0 reads and may zero
+    // RANGE's cloud; group 1 reads RANGE2's.  A cloud zeroed by the OTHER group (RANGE2 following RANGE's cloud for lack of
+    // its own is impossible: a RANGE2 plane with XYZ has its cloud) is never a predicate source afterwards.
+    for (int k = 0; k < 2; ++k) {
+        if (group[k].planes.empty()) continue;
+        ouster_hip_fops_pred pred{};
+        pred.kind = OUSTER_HIP_FOPS_PRED_XYZ;
+        pred.src_type = opt_.xyz_f64 ? OUSTER_HIP_F64 : OUSTER_HIP_F32;
+        pred.src = d_xyz_[k].data();
+        pred.axis = static_cast<uint32_t>(axis);
+        pred.lower = lower;
+        pred.upper = upper;
+        fops_invalidate_(&pred, group[k]);
+    }
+}
+
 void DeviceFrameBatch::sync() { ctx_->sync(); }
 
 double DeviceFrameBatch::tune_placement(int tries, std::vector<double>* all_ms, size_t ballast_bytes) {

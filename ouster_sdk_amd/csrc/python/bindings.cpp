@@ -15,6 +15,7 @@
 
 #include <pybind11/functional.h>
 
+#include "ouster/core/frame_ops.h"
 #include "ouster/core/image_processing.h"
 #include "ouster/core/lidar_scan.h"
 #include "ouster/hip/frame_stream.h"
@@ -772,6 +773,44 @@ PYBIND11_MODULE(core, m) {
             return py::make_tuple(p, c, t);
         },
         py::arg("frame"), py::arg("xyzlut"), py::arg("min_range"), py::arg("max_range"));
+
+    // frame_ops (python/src/cpp/client: clip, filter_field, _frame_ops_filter_uv, _frame_ops_mask, select_by_index[_metadata],
+    // reduce_by_factor[_metadata]); the Python face with the reference's call shapes is ouster.sdk.core.frame_ops
+    {
+        namespace fo = ouster::sdk::core::frame_ops;
+        m.def("clip", &fo::clip, py::arg("frame"), py::arg("fields"), py::arg("lower"), py::arg("upper"), py::arg("invalid") = 0.0);
+        m.def(
+            "filter_field",
+            [](LidarFrame& frame, const std::string& field, double lower, double upper, double invalid,
+               const py::object& filtered_fields) {
+                if (filtered_fields.is_none()) return fo::filter_field(frame, field, lower, upper, invalid, nullptr);
+                const auto names = filtered_fields.cast<std::vector<std::string>>();
+                fo::filter_field(frame, field, lower, upper, invalid, &names);
+            },
+            py::arg("frame"), py::arg("field"), py::arg("lower"), py::arg("upper"), py::arg("invalid") = 0.0,
+            py::arg("filtered_fields") = py::none());
+        m.def(
+            "_frame_ops_filter_uv",
+            [](LidarFrame& frame, const std::string& coord_2d, size_t lower, size_t upper, double invalid,
+               const std::vector<std::string>& filtered_fields, bool has_filtered_fields) {
+                fo::filter_uv(frame, coord_2d, lower, upper, invalid, has_filtered_fields ? &filtered_fields : nullptr);
+            },
+            py::arg("frame"), py::arg("coord_2d"), py::arg("lower"), py::arg("upper"), py::arg("invalid"),
+            py::arg("filtered_fields"), py::arg("has_filtered_fields"));
+        m.def(
+            "_frame_ops_mask",
+            [](LidarFrame& frame, const std::vector<std::string>& fields,
+               const py::array_t<uint8_t, py::array::c_style | py::array::forcecast>& mask, double invalid) {
+                if (mask.ndim() != 2) throw std::invalid_argument("Used mask size doesn't match frame size");
+                fo::impl::mask_value(frame, fields, ImgRef<const uint8_t>(mask.data(), static_cast<size_t>(mask.shape(0)), static_cast<size_t>(mask.shape(1))), invalid);
+            },
+            py::arg("frame"), py::arg("fields"), py::arg("mask"), py::arg("invalid") = 0.0);   // invalid: extension, for filter_xyz
+        m.def("reduce_factor_to_indices", &fo::reduce_factor_to_indices, py::arg("factor"), py::arg("height"));
+        m.def("select_by_index_metadata", &fo::select_by_index_metadata, py::arg("metadata"), py::arg("indices"));
+        m.def("select_by_index", &fo::select_by_index, py::arg("frame"), py::arg("indices"), py::arg("update_metadata") = false);
+        m.def("reduce_by_factor_metadata", &fo::reduce_by_factor_metadata, py::arg("metadata"), py::arg("factor"));
+        m.def("reduce_by_factor", &fo::reduce_by_factor, py::arg("frame"), py::arg("factor"), py::arg("update_metadata") = false);
+    }
 
     // AutoExposure / BeamUniformityCorrector (python/src/cpp/client/processing.cpp of the reference): update() works in place on
     // C-contiguous 2-D float32 / float64 arrays and converts nothing -- any other array is a TypeError (py::arg().noconvert()).
