@@ -13,15 +13,17 @@ HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++20 -fPIC -Wno-unused-result $(if $
 OBJ := $(CSRC)/_build
 SPEC_IDS := 0 1 2 3 4 5
 STREAM_IDS := 1 2 3 4 5
-HIP_OBJS := $(foreach i,$(SPEC_IDS),$(OBJ)/k_decode_$(i).o) $(foreach i,$(STREAM_IDS),$(OBJ)/k_decode_stream_$(i).o) $(OBJ)/k_standalone.o $(OBJ)/k_image.o $(OBJ)/k_frame_ops.o $(OBJ)/decode_launch.o $(OBJ)/decode_plan.o $(OBJ)/ouster_hip_capi.o $(OBJ)/host_pool.o
-HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/wide_tile.h $(CSRC)/k_image.h $(CSRC)/k_frame_ops.h include/ouster_hip.h
+HIP_OBJS := $(foreach i,$(SPEC_IDS),$(OBJ)/k_decode_$(i).o) $(foreach i,$(STREAM_IDS),$(OBJ)/k_decode_stream_$(i).o) $(OBJ)/k_standalone.o $(OBJ)/k_image.o $(OBJ)/k_frame_ops.o $(OBJ)/decode_launch.o $(OBJ)/decode_plan.o $(OBJ)/standalone_plan.o $(OBJ)/ouster_hip_capi.o $(OBJ)/host_pool.o
+HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/standalone_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/wide_tile.h $(CSRC)/k_image.h $(CSRC)/k_frame_ops.h include/ouster_hip.h
 ROCM ?= /opt/rocm
 CXXFLAGS := -O2 -std=c++17 -fPIC -pthread -Wall -Wextra -Iinclude -I$(CSRC)/host -I$(ROCM)/include -D__HIP_PLATFORM_AMD__
 
 PYEXT := ouster_sdk_amd/core$(shell python3-config --extension-suffix)
 PYINC := $(shell python3 -m pybind11 --includes)
 
-all: $(LIB)/libouster_hip.so $(LIB)/libouster_core_amd.so $(PYEXT) oracle cpptests
+PLAN_TOOL := tools/_build/standalone_plan_tool
+
+all: $(LIB)/libouster_hip.so $(LIB)/libouster_core_amd.so $(PYEXT) oracle cpptests $(PLAN_TOOL)
 
 $(OBJ)/k_decode_stream_%.o: $(CSRC)/k_decode_stream.hip $(HIP_HDRS)
 	@mkdir -p $(OBJ)
@@ -50,6 +52,16 @@ $(OBJ)/decode_plan.o: $(CSRC)/decode_plan.cpp $(CSRC)/decode_plan.h include/oust
 	@mkdir -p $(OBJ)
 	$(CXX) -O3 -std=c++17 -fPIC -Wall -Wextra -c -o $@ $<
 
+# so is the launch plan of the standalone kernels
+$(OBJ)/standalone_plan.o: $(CSRC)/standalone_plan.cpp $(CSRC)/standalone_plan.h
+	@mkdir -p $(OBJ)
+	$(CXX) -O3 -std=c++17 -fPIC -Wall -Wextra -c -o $@ $<
+
+# and evaluated on the CPU by a tool of its own: g++ only, no HIP header or library (tests/test_standalone_plan.py)
+$(PLAN_TOOL): tools/standalone_plan_tool.cpp $(CSRC)/standalone_plan.cpp $(CSRC)/standalone_plan.h
+	@mkdir -p tools/_build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -o $@ tools/standalone_plan_tool.cpp $(CSRC)/standalone_plan.cpp
+
 $(LIB)/libouster_hip.so: $(HIP_OBJS)
 	mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(HIP_OBJS)
@@ -68,6 +80,6 @@ cpptests: $(LIB)/libouster_core_amd.so
 	$(MAKE) -C oracle -s refcpptests
 
 clean:
-	rm -rf $(LIB) $(OBJ) oracle/_build tests/cpp/_build
+	rm -rf $(LIB) $(OBJ) oracle/_build tests/cpp/_build tools/_build
 
 .PHONY: all oracle clean cpptests

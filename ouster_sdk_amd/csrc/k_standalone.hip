@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "kernels_common.h"
+#include "standalone_plan.h"
 
 namespace ouster_hip_dev {
 
@@ -44,7 +45,6 @@ const FieldC* spec_fields(int spec_id, int* nf, uint32_t* chan, int* r1, int* r2
 // Rows that do not fit the LDS budget (or are not 16 B granular) take the direct path below.
 //   offset arithmetic: destagger_into, impl/lidar_frame_impl.h:753-759
 // ------------------------------------------------------------------------------------
-constexpr uint32_t DESTAGGER_LDS_MAX = 64u << 10;
 // k_destagger_rows: the same for short rows, several consecutive rows per workgroup, software pipelined: the aligned 16 B
 // loads of row j + 1 are in flight while row j is assembled from its LDS image and stored.  (Built to overlap the two
 // directions of the PCIe link for a host image worked on in place; it does not -- a kernel that reads and writes host memory
@@ -1807,58 +1807,38 @@ __global__ __launch_bounds__(256) void k_osf_unpack(OsfUnpackArgs a) {
 // ------------------------------------------------------------------------------------
 // launchers (host)
 // ------------------------------------------------------------------------------------
+// which kernel and which launch shape: standalone_plan.cpp (plain C++, tested on the CPU); the launchers only launch
 hipError_t launch_destagger(const DestaggerArgs& a, uint32_t n_images, hipStream_t st) {
-    dim3 grid(a.h, n_images);
     const size_t row_bytes = (size_t)a.w * a.elem;
-    const bool al = (row_bytes % 16 == 0) && ((((uintptr_t)a.src | (uintptr_t)a.dst) & 15) == 0);
+    const bool pointers_aligned = (((uintptr_t)a.src | (uintptr_t)a.dst) & 15) == 0;
     static const int rows_env = [] { const char* e = getenv("OUSTER_HIP_DESTAGGER_ROWS"); return e ? atoi(e) : -1; }();   // A/B
-    if (al && row_bytes <= (rows_env > 0 ? (16u << 10) : (4u << 10)) && rows_env != 0) {
-        // rows of up to 4 KB (8 / 16-bit planes of a 2048-column frame): two rows per workgroup, pipelined -- 0.77 / 0.79 of the HBM
-        // roofline on 256 images against 0.72 / 0.75 for one row per workgroup (round 6, same box); 8 KB rows (32-bit planes)
-        // lose with this form (0.50 against 0.76) and stay on k_destagger
-        uint32_t rpw = rows_env > 0 ? (uint32_t)rows_env : 2u;
-        const uint32_t nchunk = (uint32_t)(row_bytes >> 4), ch = (nchunk + 255) / 256;
-        dim3 g2((a.h + rpw - 1) / rpw, n_images);
-        const uint32_t lds2 = 2u * (uint32_t)row_bytes;
-        if (ch <= 1) hipLaunchKernelGGL(k_destagger_rows<1>, g2, dim3(256), lds2, st, a, rpw);
-        else if (ch <= 2) hipLaunchKernelGGL(k_destagger_rows<2>, g2, dim3(256), lds2, st, a, rpw);
-        else hipLaunchKernelGGL(k_destagger_rows<4>, g2, dim3(256), lds2, st, a, rpw);
-        return hipGetLastError();
+    const DestaggerPlan p = plan_destagger(row_bytes, pointers_aligned, rows_env, a.h, n_images);
+    const dim3 grid(p.grid_x, p.grid_y);
+    switch (p.route) {
+        case DestaggerRoute::ROWS1: hipLaunchKernelGGL(k_destagger_rows<1>, grid, dim3(256), p.lds_bytes, st, a, p.rows_per_wg); break;
+        case DestaggerRoute::ROWS2: hipLaunchKernelGGL(k_destagger_rows<2>, grid, dim3(256), p.lds_bytes, st, a, p.rows_per_wg); break;
+        case DestaggerRoute::ROWS4: hipLaunchKernelGGL(k_destagger_rows<4>, grid, dim3(256), p.lds_bytes, st, a, p.rows_per_wg); break;
+        default: hipLaunchKernelGGL(k_destagger, grid, dim3(256), p.lds_bytes, st, a, p.lds_bytes); break;
     }
-    const uint32_t lds = (al && row_bytes <= DESTAGGER_LDS_MAX) ? (uint32_t)row_bytes : 0u;
-    hipLaunchKernelGGL(k_destagger, grid, dim3(256), lds, st, a, lds);
     return hipGetLastError();
 }
 
 // tile width of the standalone tiled kernels.  Unlike the 14-stream k_decode these one/two-stream
 // kernels gain nothing from 256-column tiles (same-box A/B: equal for f32, 5-10 % slower for f64 and
 // full-LUT), so 64 stays the default; OUSTER_HIP_CT_TILE=256 is kept for experiments.
-static uint32_t standalone_tile_width(uint32_t w) {
+static uint32_t standalone_tile_width() {
     static const int env = [] { const char* e = getenv("OUSTER_HIP_CT_TILE"); return e ? atoi(e) : 0; }();
-    (void)w;
     return env == 256 ? 256u : 64u;
 }
 
 hipError_t launch_cartesian(const CartesianArgs& a_in, int mode, hipStream_t st) {
     CartesianArgs a = a_in;
-    if (a.vec_ok && a.w % 4 == 0) {
-        // enough workgroups to fill the chip: split the rows when the batch is small
-        const uint32_t tw = standalone_tile_width(a.w);
-        const uint32_t tiles = (a.w + tw - 1) / tw;
-        uint32_t rpb = a.h;
-        while (rpb > 16 && (size_t)tiles * a.n_images * ((a.h + rpb - 1) / rpb) < 1024) rpb = (rpb + 1) / 2;
-        rpb = (rpb + 15) / 16 * 16;
-        a.rows_per_block = rpb;
-        // as many images per workgroup as leave >= 2048 workgroups (16 at most): a full LUT's rows / the separable
-        // directions of a row are fetched / computed once per group, and the group's range quads are fetched four deep
-        uint32_t ipb = 1;
-        {
-            const size_t per_image = (size_t)tiles * ((a.h + rpb - 1) / rpb);
-            while (ipb < 16 && ipb * 2 <= a.n_images && per_image * ((a.n_images + ipb * 2 - 1) / (ipb * 2)) >= 2048) ipb *= 2;
-        }
-        a.images_per_block = ipb;
-        dim3 grid(tiles * ((a.h + rpb - 1) / rpb), (a.n_images + ipb - 1) / ipb);
-        if (tw == 256) {
+    const TiledPlan p = plan_cartesian(a.w, a.h, a.n_images, a.vec_ok != 0, standalone_tile_width());
+    const dim3 grid(p.grid_x, p.grid_y);
+    if (p.tiled) {
+        a.rows_per_block = p.rows_per_block;
+        a.images_per_block = p.images_per_block;
+        if (p.tile_width == 256) {
             switch (mode) {
                 case 1: hipLaunchKernelGGL((k_cartesian_tiled<1, 256>), grid, dim3(256), 0, st, a); break;
                 case 2: hipLaunchKernelGGL((k_cartesian_tiled<2, 256>), grid, dim3(256), 0, st, a); break;
@@ -1873,11 +1853,6 @@ hipError_t launch_cartesian(const CartesianArgs& a_in, int mode, hipStream_t st)
         }
         return hipGetLastError();
     }
-    const size_t quads = ((size_t)a.w * a.h + 3) / 4 * a.n_images;
-    size_t blocks = (quads + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (blocks == 0) blocks = 1;
-    dim3 grid((uint32_t)blocks);
     switch (mode) {
         case 1: hipLaunchKernelGGL(k_cartesian<1>, grid, dim3(256), 0, st, a); break;
         case 2: hipLaunchKernelGGL(k_cartesian<2>, grid, dim3(256), 0, st, a); break;
@@ -1888,15 +1863,12 @@ hipError_t launch_cartesian(const CartesianArgs& a_in, int mode, hipStream_t st)
 
 hipError_t launch_dewarp(const DewarpArgs& a_in, hipStream_t st) {
     DewarpArgs a = a_in;
-    if (a.w % 4 == 0 && (((uintptr_t)a.points | (uintptr_t)a.out) & 15) == 0) {
-        const uint32_t tw = standalone_tile_width(a.w);
-        const uint32_t tiles = (a.w + tw - 1) / tw;
-        uint32_t rpb = a.h;
-        while (rpb > 16 && (size_t)tiles * a.n_images * ((a.h + rpb - 1) / rpb) < 1024) rpb = (rpb + 1) / 2;
-        rpb = (rpb + 15) / 16 * 16;
-        a.rows_per_block = rpb;
-        dim3 grid(tiles * ((a.h + rpb - 1) / rpb), a.n_images);
-        if (tw == 256) {
+    const bool aligned = (((uintptr_t)a.points | (uintptr_t)a.out) & 15) == 0;
+    const TiledPlan p = plan_dewarp(a.w, a.h, a.n_images, aligned, standalone_tile_width());
+    const dim3 grid(p.grid_x, p.grid_y);
+    if (p.tiled) {
+        a.rows_per_block = p.rows_per_block;
+        if (p.tile_width == 256) {
             if (a.dtype == OUSTER_HIP_F32) hipLaunchKernelGGL((k_dewarp_tiled<float, 256>), grid, dim3(256), 0, st, a);
             else hipLaunchKernelGGL((k_dewarp_tiled<double, 256>), grid, dim3(256), 0, st, a);
         } else {
@@ -1905,12 +1877,8 @@ hipError_t launch_dewarp(const DewarpArgs& a_in, hipStream_t st) {
         }
         return hipGetLastError();
     }
-    const size_t total = (size_t)a.w * a.h * a.n_images;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (blocks == 0) blocks = 1;
-    if (a.dtype == OUSTER_HIP_F32) hipLaunchKernelGGL(k_dewarp<float>, dim3((uint32_t)blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_dewarp<double>, dim3((uint32_t)blocks), dim3(256), 0, st, a);
+    if (a.dtype == OUSTER_HIP_F32) hipLaunchKernelGGL(k_dewarp<float>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_dewarp<double>, grid, dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
