@@ -208,6 +208,24 @@ class DeviceFrameBatch {
     /** Per-column body_to_world poses of one frame (w x 16 doubles, row-major 4x4 each; identity
      *  until set), the input of dewarp(). */
     void upload_poses(uint32_t frame, const double* poses_w_by_16);
+    /** The poses made where the timestamps are: every valid column (status & 1) of every frame gets core::interp_pose of the
+     *  known trajectory at its timestamp * 1e-9 s (core/pose_util.h; what the reference's deskew does per frame with
+     *  set_column_pose); the other columns keep the pose they have -- identity on a fresh batch.  x_known_s in seconds,
+     *  strictly increasing; timestamps outside extrapolate with the first / last pair.  Asynchronous on the batch's stream,
+     *  after decode(); one launch for the whole batch, which also writes the float rows dewarp() of a float batch reads: the
+     *  next dewarp() / dewarp_async() uses the new poses.  A world-frame batch (BatchOptions::xyz_world_frame) applies poses
+     *  inside decode(): clouds already decoded are not rewritten, the new poses hold from the next decode().
+     *  @throw std::invalid_argument with the reference's messages (sizes, fewer than two poses, x_known not increasing) */
+    void interp_poses(const std::vector<double>& x_known_s, const std::vector<core::mat4d>& poses_known);
+    /** Two known poses, any sign of t1 - t0.  @throw std::invalid_argument for |t1 - t0| < epsilon */
+    void interp_poses(double t0, const core::mat4d& x0, double t1, const core::mat4d& x1);
+    /** One frame's poses (w x 16 doubles; synchronous). */
+    void download_poses(uint32_t frame, double* poses_w_by_16);
+    /** [n_frames][w][16] doubles; identity until set (allocated on first use). */
+    double* poses_device();
+    /** Rows 0..2 of the same poses cast to float, [n_frames][w][12]: what dewarp() of a float batch multiplies with.  nullptr
+     *  for an xyz_f64 batch (it reads poses_device()). */
+    const float* pose_rows_device();
     /** Range-gated, compacting dewarp of the whole decoded batch, on the device
      *  (core::dewarp(FrameSet, luts, min_range, max_range) with provenance, pose_util.h:475-493 /
      *  impl/dewarp_impl.h:86-115): RANGE planes + status + poses -> world-frame points of type

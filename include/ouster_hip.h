@@ -193,7 +193,8 @@ int ouster_hip_ctx_device(ouster_hip_ctx* ctx); /* the HIP device ordinal the co
  *   "retune" 1: forget the variant tuner's verdicts (a caller that re-allocated its buffers re-learns)
  *   "stream" -1 auto | 0 never | 128/256 force k_decode_stream's tile width   "stream_rows" rows of its tiles
  *   "stream_wait" 0: trust the in-order vmcnt instead of draining it before a prefetched tile is used
- *   "stream_min_tiles" tiles per persistent workgroup below which a launch stays on the one-tile kernels */
+ *   "stream_min_tiles" tiles per persistent workgroup below which a launch stays on the one-tile kernels
+ *   "pose_direct" 1: k_pose_interp stores every lane's own row instead of staging a workgroup's rows in LDS (A/B) */
 int ouster_hip_ctx_set_knob(ouster_hip_ctx* ctx, const char* name, int value);
 int ouster_hip_sync(ouster_hip_ctx* ctx);
 const char* ouster_hip_last_error(void);
@@ -588,6 +589,52 @@ int ouster_hip_ctx_set_tuning_cache(ouster_hip_ctx* ctx, const char* path);
 /* How the last ouster_hip_decode chose its variant: "cache" (read from the file), "measured" (timed by this context),
  * "measuring" (still timing: the call ran a candidate) or "none" (forced by a knob / a shape with one variant). */
 const char* ouster_hip_last_decode_tuner(ouster_hip_ctx* ctx);
+
+/* ---- interp_pose / transform ------------------------------------------------ */
+/* Replaces interp_pose (ouster_core/include/ouster/core/pose_util.h:194-434) and transform (:118-173).  Poses are row-major
+ * 4x4 doubles.  The known poses travel as host arrays: what is computed once per pair of them -- log(inv(a) b) / (t1 - t0),
+ * src/transform_homogeneous.cpp:31-62 -- is done on the host, the per-x work -- a exp((x - t0) scaled_twist),
+ * src/transform_vector.cpp:40-60, 96-104 -- on the GPU, always in double; the result is cast to the output type as the
+ * reference casts it.  The segment of an x is min(k - 2, #{j >= 1 : x_known[j] <= x}): the first / last segment extrapolate.
+ * Validation fails with OUSTER_HIP_ERR_INVALID_ARGUMENT and the reference's message before anything touches the GPU:
+ * k < 2, x_known not strictly increasing (every pair is checked), |t1 - t0| < DBL_EPSILON in the pair forms, and -- where x_interp
+ * is host memory -- x_interp[i] < x_interp[i - 1] anywhere (a superset of where the reference throws).  x_interp in device
+ * memory is not read by the host: every x is evaluated on its own, in any order. */
+
+/* The per-segment table, [k - 1][24] doubles: t0, a[16], scaled_twist[6] (rotation then translation), one pad.  Pure host
+ * function, no GPU needed. */
+int ouster_hip_pose_segments(const double* x_known, const double* poses_known, uint32_t k, double* segments);
+/* The validation alone, pure host as well: the known poses as above and, when x_interp (HOST, n values) is not NULL, that it
+ * never decreases.  What the C++ mirror calls before it asks for a GPU. */
+int ouster_hip_pose_validate(const double* x_known, const double* poses_known, uint32_t k, const double* x_interp, uint64_t n);
+/* x_interp_dev [n] f64 (device) -> poses_out_dev [n][16] of dtype (OUSTER_HIP_F32 / OUSTER_HIP_F64), 16-byte aligned.
+ * Asynchronous on the context's stream; n == 0 is a no-op. */
+int ouster_hip_interp_pose(ouster_hip_ctx* ctx, const double* x_interp_dev, uint64_t n, const double* x_known,
+                           const double* poses_known, uint32_t k, int dtype, void* poses_out_dev);
+/* The same on host arrays (pool memory in place, anything else through the context's grow-only scratch); synchronous. */
+int ouster_hip_interp_pose_host(ouster_hip_ctx* ctx, const double* x_interp, uint64_t n, const double* x_known,
+                                const double* poses_known, uint32_t k, int dtype, void* poses_out);
+/* Two known poses, any sign of t1 - t0 (pose_util.h:316-326): every x on the one segment.  Not expressible through the
+ * trajectory forms, whose x_known must increase. */
+int ouster_hip_interp_pose_pair_host(ouster_hip_ctx* ctx, const double* x_interp, uint64_t n, double t0, const double* x0,
+                                     double t1, const double* x1, int dtype, void* poses_out);
+/* Per-column poses of frames resident in HBM: timestamp_dev [n_frames][w] u64 ns, status_dev [n_frames][w] u32.  A column
+ * with status & 1 gets its pose at double(timestamp) * 1e-9 s into poses_dev [n_frames][w][16] f64 and, when pose_rows_dev is
+ * not NULL, float(pose[0..11]) into pose_rows_dev [n_frames][w][12] (the input of ouster_hip_dewarp_frames_rows); the other
+ * columns' 128 B and 48 B are left as they are.  One launch, asynchronous. */
+int ouster_hip_interp_pose_columns(ouster_hip_ctx* ctx, const uint64_t* timestamp_dev, const uint32_t* status_dev,
+                                   uint32_t n_frames, uint32_t w, const double* x_known, const double* poses_known,
+                                   uint32_t k, double* poses_dev, float* pose_rows_dev);
+/* The column form on two known poses, any sign of t1 - t0 (what DeviceFrameBatch::interp_poses(t0, x0, t1, x1) queues): every
+ * valid column on the one segment, outputs and untouched bytes as above. */
+int ouster_hip_interp_pose_pair_columns(ouster_hip_ctx* ctx, const uint64_t* timestamp_dev, const uint32_t* status_dev,
+                                        uint32_t n_frames, uint32_t w, double t0, const double* x0, double t1,
+                                        const double* x1, double* poses_dev, float* pose_rows_dev);
+/* transform<T>(transformed, points, pose) (pose_util.h:118-131): R p + t in the points' type (dtype F32 / F64), the pose
+ * (16 host doubles) cast to that type first.  points / out [n][3] in device memory, may alias.  Asynchronous. */
+int ouster_hip_transform(ouster_hip_ctx* ctx, const void* points_dev, const double* pose16, void* out_dev, int dtype,
+                         uint64_t n);
+int ouster_hip_transform_host(ouster_hip_ctx* ctx, const void* points, const double* pose16, void* out, int dtype, uint64_t n);
 
 #ifdef __cplusplus
 }

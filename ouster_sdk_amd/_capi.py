@@ -130,6 +130,10 @@ ABI_SYMBOLS = [
     "ouster_hip_frame_ops_invalid_bits", "ouster_hip_frame_ops_clip", "ouster_hip_frame_ops_invalidate",
     "ouster_hip_frame_ops_select_rows", "ouster_hip_frame_ops_clip_host", "ouster_hip_frame_ops_invalidate_host",
     "ouster_hip_frame_ops_select_rows_host",
+    # interp_pose / transform
+    "ouster_hip_pose_segments", "ouster_hip_pose_validate", "ouster_hip_interp_pose", "ouster_hip_interp_pose_host", "ouster_hip_interp_pose_pair_host",
+    "ouster_hip_interp_pose_columns", "ouster_hip_interp_pose_pair_columns", "ouster_hip_transform",
+    "ouster_hip_transform_host",
 ]
 
 _hip = None
@@ -243,6 +247,17 @@ def load_hip(private_path: Optional[str] = None):
         L.ouster_hip_frame_ops_invalidate_host.argtypes = [vp, C.POINTER(FopsPred), C.POINTER(FopsPlane), u32, u32, u32]
         L.ouster_hip_frame_ops_select_rows_host.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32), u32, u32, u32,
                                                             C.POINTER(u32), u32]
+    if hasattr(L, "ouster_hip_interp_pose"):   # absent only in older A/B builds loaded via OUSTER_HIP_SO
+        u32, u64, dbl = C.c_uint32, C.c_uint64, C.c_double
+        L.ouster_hip_pose_segments.argtypes = [vp, vp, u32, vp]
+        L.ouster_hip_pose_validate.argtypes = [vp, vp, u32, vp, u64]
+        L.ouster_hip_interp_pose.argtypes = [vp, vp, u64, vp, vp, u32, C.c_int, vp]
+        L.ouster_hip_interp_pose_host.argtypes = [vp, vp, u64, vp, vp, u32, C.c_int, vp]
+        L.ouster_hip_interp_pose_pair_host.argtypes = [vp, vp, u64, dbl, vp, dbl, vp, C.c_int, vp]
+        L.ouster_hip_interp_pose_columns.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, vp, vp]
+        L.ouster_hip_interp_pose_pair_columns.argtypes = [vp, vp, vp, u32, u32, dbl, vp, dbl, vp, vp, vp]
+        L.ouster_hip_transform.argtypes = [vp, vp, vp, vp, C.c_int, u64]
+        L.ouster_hip_transform_host.argtypes = [vp, vp, vp, vp, C.c_int, u64]
     if private_path is None:
         _hip = L
     return L

@@ -94,6 +94,7 @@ struct Knobs {
     int dewarp_single_pass = 0, beam_lds = 1, fixup = 1, small = 1, fixup_rows = 0, hdr_words = 1, fixup_wide = 1;
     int stream = -1, stream_rows = 0, stream_wait = 1, stream_min_tiles = 8, stream_order = 0, slotmap = 1;
     int dwf_stream = -1, stream_loader = 4;
+    int pose_direct = 0;
 };
 struct KnobDef {
     const char* name;    // ouster_hip_ctx_set_knob

@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime_api.h>
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <map>
 
 #include <cstring>
@@ -704,6 +706,47 @@ void DeviceFrameBatch::upload_poses(uint32_t frame, const double* poses) {
             d_pose_rows_.upload(rows.data(), rows_per * 4, rows_per * 4 * frame);
         }
     }
+}
+
+const float* DeviceFrameBatch::pose_rows_device() {
+    poses_device();
+    return opt_.xyz_f64 ? nullptr : static_cast<const float*>(d_pose_rows_.data());
+}
+
+double* DeviceFrameBatch::poses_device() {
+    if (d_poses_.size() == 0 || (!opt_.xyz_f64 && d_pose_rows_.size() == 0)) upload_poses(0, nullptr);
+    return static_cast<double*>(d_poses_.data());
+}
+
+void DeviceFrameBatch::interp_poses(const std::vector<double>& x_known, const std::vector<mat4d>& poses_known) {
+    ScopedContext on_my_context(ctx_);
+    if (x_known.size() != poses_known.size()) throw std::invalid_argument("x_known and poses_known sizes are not matching");
+    static_assert(sizeof(mat4d) == 128, "mat4d is 16 packed doubles");
+    const uint32_t k = static_cast<uint32_t>(x_known.size());
+    const double* known = poses_known.empty() ? nullptr : poses_known[0].m;
+    check(ouster_hip_pose_validate(x_known.data(), known, k, nullptr, 0));   // refuses before anything is allocated
+    double* poses = poses_device();
+    check(ouster_hip_interp_pose_columns(default_ctx(), static_cast<const uint64_t*>(d_ts_.data()),
+                                         static_cast<const uint32_t*>(d_status_.data()), n_frames_, w_, x_known.data(), known, k,
+                                         poses, opt_.xyz_f64 ? nullptr : static_cast<float*>(d_pose_rows_.data())));
+}
+
+void DeviceFrameBatch::interp_poses(double t0, const mat4d& x0, double t1, const mat4d& x1) {
+    ScopedContext on_my_context(ctx_);
+    if (std::fabs(t1 - t0) < DBL_EPSILON) throw std::invalid_argument("Cannot interpolate with zero duration between poses");
+    double* poses = poses_device();
+    check(ouster_hip_interp_pose_pair_columns(default_ctx(), static_cast<const uint64_t*>(d_ts_.data()),
+                                              static_cast<const uint32_t*>(d_status_.data()), n_frames_, w_, t0, x0.m, t1, x1.m,
+                                              poses, opt_.xyz_f64 ? nullptr : static_cast<float*>(d_pose_rows_.data())));
+}
+
+void DeviceFrameBatch::download_poses(uint32_t frame, double* poses) {
+    ScopedContext on_my_context(ctx_);
+    if (frame >= n_frames_) throw std::out_of_range("DeviceFrameBatch: frame index");
+    poses_device();
+    const size_t per = static_cast<size_t>(w_) * 128;
+    sync();
+    d_poses_.download(poses, per, per * frame);
 }
 
 uint64_t DeviceFrameBatch::dewarp(double min_range, double max_range, bool provenance) {

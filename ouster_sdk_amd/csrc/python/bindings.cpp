@@ -756,6 +756,71 @@ PYBIND11_MODULE(core, m) {
         },
         py::arg("points"), py::arg("poses"));
 
+    // interp_pose / interp_pose_float / transform: shapes, dtype dispatch and error types of python/src/cpp/client/processing.cpp:
+    // 191-338 (x (N,) or (N,1), poses (M,4,4) -> (N,4,4); points (N,3) or (H,W,3), float32 stays float32, other floats are float64)
+    {
+        auto is_float = [](const py::array& a) { return a.dtype().kind() == 'f'; };
+        auto interp = [](const py::array& x_interp, const py::array& x_known, const py::array& poses_known, bool f64) -> py::array {
+            if (x_interp.ndim() != 1 && (x_interp.ndim() != 2 || x_interp.shape(1) != 1))
+                throw std::runtime_error("x_interp must have shape (N,) or (N,1)");
+            if (x_known.ndim() != 1 && (x_known.ndim() != 2 || x_known.shape(1) != 1))
+                throw std::runtime_error("x_known must have shape (N,) or (N,1)");
+            if (poses_known.ndim() != 3 || poses_known.shape(1) != 4 || poses_known.shape(2) != 4)
+                throw py::type_error("poses_known must have shape (M, 4, 4)");
+            if (x_known.shape(0) != poses_known.shape(0))
+                throw std::runtime_error("The number of poses in poses_known must match the number of values in x_known");
+            auto xi = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(x_interp);
+            auto xk = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(x_known);
+            // interp_pose_float takes float poses: through float first, as the reference's ensure_c_contig_floating<float> does
+            py::array_t<double, py::array::c_style | py::array::forcecast> pk;
+            if (f64) pk = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(poses_known);
+            else pk = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(
+                     py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(poses_known));
+            if (!xi || !xk || !pk) throw py::type_error("interp_pose: arrays of numbers expected");
+            const size_t n = static_cast<size_t>(xi.shape(0)), k = static_cast<size_t>(xk.shape(0));
+            const std::vector<py::ssize_t> shape = {static_cast<py::ssize_t>(n), 4, 4};
+            if (f64) {
+                py::array_t<double> out(shape);
+                impl::interp_pose_device(xi.data(), n, xk.data(), pk.data(), k, true, out.mutable_data());
+                return std::move(out);
+            }
+            py::array_t<float> out(shape);
+            impl::interp_pose_device(xi.data(), n, xk.data(), pk.data(), k, false, out.mutable_data());
+            return std::move(out);
+        };
+        m.def("interp_pose", [interp](const py::array& a, const py::array& b, const py::array& c) { return interp(a, b, c, true); },
+              py::arg("x_interp"), py::arg("x_known"), py::arg("poses_known"));
+        m.def("interp_pose_float", [interp](const py::array& a, const py::array& b, const py::array& c) { return interp(a, b, c, false); },
+              py::arg("x_interp"), py::arg("x_known"), py::arg("poses_known"));
+        m.def(
+            "transform",
+            [is_float](const py::array& points, const py::array& pose) -> py::array {
+                if (!is_float(points) || !is_float(pose)) throw py::type_error("points and pose must be floating-point arrays");
+                if (pose.ndim() != 2 || pose.shape(0) != 4 || pose.shape(1) != 4) throw py::type_error("pose must have shape (4, 4)");
+                std::vector<py::ssize_t> shape;
+                if (points.ndim() == 2 && points.shape(1) == 3) shape = {points.shape(0), 3};
+                else if (points.ndim() == 3 && points.shape(2) == 3) shape = {points.shape(0), points.shape(1), 3};
+                else throw std::invalid_argument("points array must have shape (n, 3) or (h, w, 3)");
+                const size_t n = static_cast<size_t>(points.size() / 3);
+                const bool f32 = points.dtype().is(py::dtype::of<float>());
+                // the pose in the points' type first (transform_any<T>), then handed over as doubles: exact for float
+                auto po = f32 ? py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(
+                                    py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(pose))
+                              : py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(pose);
+                if (f32) {
+                    auto pt = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(points);
+                    py::array_t<float> out(shape);
+                    impl::transform_device(pt.data(), po.data(), out.mutable_data(), false, n);
+                    return std::move(out);
+                }
+                auto pt = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(points);
+                py::array_t<double> out(shape);
+                impl::transform_device(pt.data(), po.data(), out.mutable_data(), true, n);
+                return std::move(out);
+            },
+            py::arg("points"), py::arg("pose"));
+    }
+
     // extension over the reference's Python surface: the C++ dewarp(LidarFrame, XYZLut, min_range,
     // max_range) with provenance (pose_util.h:456-485, impl/dewarp_impl.h:23-81)
     m.def(
