@@ -6,16 +6,17 @@ HIPCC ?= hipcc
 CXX ?= g++
 LIB := ouster_sdk_amd/lib
 CSRC := ouster_sdk_amd/csrc
-# host/pose_util.cpp is the plain C++ half of interp_pose inside libouster_hip.so (an object of its own, below)
-HOST_SRC := $(filter-out $(CSRC)/host/pose_util.cpp,$(wildcard $(CSRC)/host/*.cpp))
+# host/pose_util.cpp and host/normals_util.cpp are the plain C++ halves of interp_pose and normals inside libouster_hip.so (objects of
+# their own, below)
+HOST_SRC := $(filter-out $(CSRC)/host/pose_util.cpp $(CSRC)/host/normals_util.cpp,$(wildcard $(CSRC)/host/*.cpp))
 # EXPERIMENTS=1 also compiles the measured-slower kernel forms kept for A/B work (k_decode_wide_resolved, k_dwf_single, k_dwf_fused)
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++20 -fPIC -Wno-unused-result $(if $(EXPERIMENTS),-DOUSTER_EXPERIMENTS,)
 # the fused decode kernels are compiled once per packet-profile specialisation (parallel with -j)
 OBJ := $(CSRC)/_build
 SPEC_IDS := 0 1 2 3 4 5
 STREAM_IDS := 1 2 3 4 5
-HIP_OBJS := $(foreach i,$(SPEC_IDS),$(OBJ)/k_decode_$(i).o) $(foreach i,$(STREAM_IDS),$(OBJ)/k_decode_stream_$(i).o) $(OBJ)/k_standalone.o $(OBJ)/k_image.o $(OBJ)/k_frame_ops.o $(OBJ)/k_pose.o $(OBJ)/pose_util.o $(OBJ)/decode_launch.o $(OBJ)/decode_plan.o $(OBJ)/standalone_plan.o $(OBJ)/ouster_hip_capi.o $(OBJ)/host_pool.o
-HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/standalone_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/wide_tile.h $(CSRC)/k_image.h $(CSRC)/k_frame_ops.h $(CSRC)/k_pose.h $(CSRC)/pose_host.h include/ouster_hip.h
+HIP_OBJS := $(foreach i,$(SPEC_IDS),$(OBJ)/k_decode_$(i).o) $(foreach i,$(STREAM_IDS),$(OBJ)/k_decode_stream_$(i).o) $(OBJ)/k_standalone.o $(OBJ)/k_image.o $(OBJ)/k_frame_ops.o $(OBJ)/k_pose.o $(OBJ)/pose_util.o $(OBJ)/k_normals.o $(OBJ)/normals_util.o $(OBJ)/decode_launch.o $(OBJ)/decode_plan.o $(OBJ)/standalone_plan.o $(OBJ)/ouster_hip_capi.o $(OBJ)/host_pool.o
+HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/standalone_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/wide_tile.h $(CSRC)/k_image.h $(CSRC)/k_frame_ops.h $(CSRC)/k_pose.h $(CSRC)/pose_host.h $(CSRC)/k_normals.h $(CSRC)/normals_host.h include/ouster_hip.h
 ROCM ?= /opt/rocm
 CXXFLAGS := -O2 -std=c++17 -fPIC -pthread -Wall -Wextra -Iinclude -I$(CSRC)/host -I$(ROCM)/include -D__HIP_PLATFORM_AMD__
 
@@ -58,6 +59,16 @@ $(OBJ)/pose_util.o: $(CSRC)/host/pose_util.cpp $(CSRC)/pose_host.h include/ouste
 	@mkdir -p $(OBJ)
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -c -o $@ $<
 
+# normals equals a model that rounds every step on its own (tests/normals_model.py): no contraction in the kernels, none in the
+# host half that makes the per-call constants with libm
+$(OBJ)/k_normals.o: $(CSRC)/k_normals.hip $(HIP_HDRS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
+
+$(OBJ)/normals_util.o: $(CSRC)/host/normals_util.cpp $(CSRC)/normals_host.h include/ouster_hip.h
+	@mkdir -p $(OBJ)
+	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -c -o $@ $<
+
 # the launch plan is plain C++ (tests/cpp builds the same file without HIP)
 $(OBJ)/decode_plan.o: $(CSRC)/decode_plan.cpp $(CSRC)/decode_plan.h include/ouster_hip.h
 	@mkdir -p $(OBJ)
@@ -77,10 +88,10 @@ $(LIB)/libouster_hip.so: $(HIP_OBJS)
 	mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(HIP_OBJS)
 
-$(LIB)/libouster_core_amd.so: $(HOST_SRC) $(wildcard include/ouster/core/*.h include/ouster/hip/*.h include/ouster/pcap/*.h include/ouster/osf/*.h) $(CSRC)/host/host_internal.h $(LIB)/libouster_hip.so
+$(LIB)/libouster_core_amd.so: $(HOST_SRC) $(wildcard include/ouster/core/*.h include/ouster/hip/*.h include/ouster/pcap/*.h include/ouster/osf/*.h include/ouster/algorithm/*.h) $(CSRC)/host/host_internal.h $(LIB)/libouster_hip.so
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRC) -L$(LIB) -louster_hip -L$(ROCM)/lib -lamdhip64 -lz -l:libzstd.so.1 -Wl,-rpath,'$$ORIGIN'
 
-$(PYEXT): $(CSRC)/python/bindings.cpp $(LIB)/libouster_core_amd.so $(wildcard include/ouster/core/*.h)
+$(PYEXT): $(CSRC)/python/bindings.cpp $(LIB)/libouster_core_amd.so $(wildcard include/ouster/core/*.h include/ouster/algorithm/*.h)
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fvisibility=hidden -Iinclude $(PYINC) -o $@ $(CSRC)/python/bindings.cpp -L$(LIB) -louster_core_amd -louster_hip -Wl,-rpath,'$$ORIGIN/lib'
 
 oracle:

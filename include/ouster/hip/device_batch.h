@@ -83,6 +83,15 @@ struct ImagePipeline {
     std::vector<core::image::BeamUniformityCorrector> beam_uniformity;   ///< empty: no correction
 };
 
+/** Parameters of DeviceFrameBatch::normals: those of algorithm::normals (algorithm/normals.h), with its defaults. */
+struct NormalsOptions {
+    uint32_t pixel_search_range = 1;
+    double min_angle_of_incidence_rad = 1 * 3.14159265358979323846 / 180.0;
+    double target_distance_m = 0.025;
+    bool dual_return = false;        ///< both returns in one launch, each a source of neighbour candidates for the other
+    bool staggered_output = false;   ///< normal i belongs to point i of xyz_device(); false: the reference's destaggered layout
+};
+
 class DeviceFrameBatch {
    public:
     /** One LUT per sensor; frame f of the batch uses sensor f % sensors.size(). */
@@ -205,6 +214,24 @@ class DeviceFrameBatch {
     void filter_xyz(int axis, double lower, double upper, double invalid = 0,
                     const std::vector<std::string>* filtered_fields = nullptr, bool world_frame = false);
 
+    /** algorithm::normals (algorithm/normals.h; csrc/k_normals.hip) of every frame of the decoded batch without leaving HBM: the
+     *  staggered RANGE (RANGE2) planes and clouds are read through the shifts the batch destaggers with -- the FIRST sensor's
+     *  pixel_shift_by_row, as for frame_ops above -- so no destaggered copy of a cloud is made.  Sensor origins follow the frame
+     *  the cloud is in: zeros for a sensor-frame batch (use_extrinsics == false), the translation of the frame's sensor's
+     *  sensor_to_body for a body-frame batch, and per column the translation of pose[v] * sensor_to_body from poses_device() for
+     *  a world-frame batch (xyz_world_frame); frame f belongs to sensor f % sensors.  The result, double [n_frames][h * w][3]
+     *  per return, is owned by the batch (allocated on the first call) and equals the float64 restatement of the reference
+     *  (tests/normals_model.py) on the batch's own cloud, ranges and poses, bit for bit.  On the batch's stream; synchronous
+     *  (the subtent round trip of ouster_hip_normals).  hip::FrameStream and hip::ShardedBatch have no normals yet.
+     *  @throw std::invalid_argument when the batch lacks BatchOptions::xyz or the RANGE plane (dual_return: RANGE2 and its cloud)
+     *  @throw std::runtime_error with the reference's messages for non-positive parameters */
+    void normals(const NormalsOptions& options = NormalsOptions());
+    /** Result of the last normals(): return_index 0 / 1; nullptr before the first call (1: before the first dual call). */
+    double* normals_device(int return_index);
+    /** One frame's normals of the last normals() (h * w x 3 doubles, in the layout that call chose; synchronous).
+     *  @throw std::invalid_argument before normals() has made that return's normals */
+    void download_normals(int return_index, uint32_t frame, double* host);
+
     /** Per-column body_to_world poses of one frame (w x 16 doubles, row-major 4x4 each; identity
      *  until set), the input of dewarp(). */
     void upload_poses(uint32_t frame, const double* poses_w_by_16);
@@ -272,6 +299,8 @@ class DeviceFrameBatch {
     DeviceBuffer d_poses_, d_dw_pts_, d_dw_fi_, d_dw_ci_, d_dw_ts_, d_dw_off_;
     DeviceBuffer d_pose_rows_;   // float output: rows 0..2 of the poses cast to float, [n_frames][w][12]
     std::vector<uint64_t> dw_offsets_;
+    std::vector<double> sensor_to_body_;   // [sensors][16], row-major
+    DeviceBuffer d_normals_[2];            // normals(): f64 [n_frames][h * w][3] per return, made on first use
     bool dw_prov_ = false;
 };
 

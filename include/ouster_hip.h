@@ -636,6 +636,58 @@ int ouster_hip_transform(ouster_hip_ctx* ctx, const void* points_dev, const doub
                          uint64_t n);
 int ouster_hip_transform_host(ouster_hip_ctx* ctx, const void* points, const double* pose16, void* out, int dtype, uint64_t n);
 
+/* ---- algorithm::normals --------------------------------------------------------- */
+/* Replaces ouster::sdk::algorithm::normals (ouster_algorithm/src/normals.cpp): unit surface normals of a range image's cloud,
+ * one f64 triple per pixel, zero where the pixel has no range or no usable neighbour.  Two launches with one small synchronous
+ * round trip between them: k_normals_subtent finds, per frame, the column the reference's compute_vertical_subtent would stop at
+ * and leaves the two beams' dot product (16 bytes per frame and return); the host applies clamp, acos and the division with libm
+ * (ouster_hip_normals_constants) and hands the constants to k_normals, which evaluates no transcendental function: its result
+ * equals a float64 restatement of the reference that rounds every operation on its own, bit for bit.
+ * Validation fails with OUSTER_HIP_ERR_INVALID_ARGUMENT and the reference's message before anything touches the GPU. */
+typedef struct ouster_hip_normals_consts {
+    double px_res_h;    /* 2 pi / (2 pi / w) */
+    double px_res_v;    /* 2 pi / subtent */
+    double tan_safe;    /* tan(max(min_angle_of_incidence_rad, 1e-6)) */
+    double target_sq;   /* target_distance_m squared */
+    double subtent;     /* vertical pixel subtent, rad */
+} ouster_hip_normals_consts;
+/* The constants of one call.  has_pair != 0: the subtent is acos(clamp(dot, -1, 1)) / rows_apart; 0: the reference's fallback,
+ * (pi / 2) / max(1, h - 1).  Pure host function, no GPU needed; refuses non-positive target_distance_m /
+ * min_angle_of_incidence_rad with the reference's messages. */
+int ouster_hip_normals_constants(uint32_t w, uint32_t h, double min_angle_of_incidence_rad, double target_distance_m, int has_pair,
+                                 double dot, uint32_t rows_apart, ouster_hip_normals_consts* out);
+typedef struct ouster_hip_normals_desc {
+    const void* xyz;               /* first return: [n_frames][h * w][3] of xyz_dtype */
+    const uint32_t* range;         /*               [n_frames][h][w], mm */
+    const void* xyz2;              /* second return; xyz2 == range2 == NULL selects the single-return form */
+    const uint32_t* range2;
+    double* normals;               /* [n_frames][h * w][3]; every element is written */
+    double* normals2;              /* dual form only */
+    const int32_t* pixel_shift_by_row; /* HOST, h entries, any sign and size: the inputs are staggered and destaggered pixel (u, v) lies
+                                      at column (v - shift[u]) mod w; NULL: the inputs are destaggered */
+    const double* sensor_origins;  /* (w, 3), one per destaggered column, shared by the frames; NULL: zeros, or from poses */
+    const double* poses;           /* [n_frames][w][16] row-major 4x4: the origin of column v is the translation of
+                                      poses[frame][v] * sensor_to_body; NULL: not used.  Ignored when sensor_origins is given */
+    const double* sensor_to_body;  /* HOST, [max(1, n_sensor_to_body)][16] doubles: frame f uses matrix f % n_sensor_to_body (a batch
+                                      that interleaves the frames of several sensors).  With poses: as above; NULL: identity.
+                                      Without poses: every column's origin is the matrix's translation (a body-frame cloud).
+                                      Ignored when sensor_origins is given */
+    uint64_t xyz_rows, xyz2_rows;  /* points per frame the clouds hold: h * w, or "normals: xyz dimensions mismatch" */
+    uint32_t n_frames, h, w;
+    uint32_t range2_h, range2_w;   /* shape of range2 (dual form): h, w, or "normals: range2 dimensions mismatch" */
+    uint32_t n_origins;            /* rows of sensor_origins where it is given: w, or "normals: sensor_origins size must match ..." */
+    uint32_t pixel_search_range;
+    uint32_t n_sensor_to_body;     /* matrices in sensor_to_body; 0 counts as 1 */
+    int32_t xyz_dtype;             /* OUSTER_HIP_F32 (widened on load, exact) / OUSTER_HIP_F64 */
+    int32_t staggered_output;      /* 1 with pixel_shift_by_row: normal i belongs to point i of the staggered cloud; 0: the
+                                      destaggered layout of the reference */
+    double min_angle_of_incidence_rad, target_distance_m;
+} ouster_hip_normals_desc;
+/* Every array but the two marked HOST in device memory.  Synchronous (the subtent round trip).  Work is queued on ctx's stream. */
+int ouster_hip_normals(ouster_hip_ctx* ctx, const ouster_hip_normals_desc* desc);
+/* The same with every array in host memory (pool memory in place, anything else through the context's grow-only scratch). */
+int ouster_hip_normals_host(ouster_hip_ctx* ctx, const ouster_hip_normals_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,21 @@ FOPS_TYPES = {"uint8": U8, "uint16": U16, "uint32": U32, "uint64": U64, "int8": 
               "int64": I64, "float32": F32, "float64": F64}
 
 
+class NormalsConsts(C.Structure):   # ouster_hip_normals_consts
+    _fields_ = [("px_res_h", C.c_double), ("px_res_v", C.c_double), ("tan_safe", C.c_double), ("target_sq", C.c_double),
+                ("subtent", C.c_double)]
+
+
+class NormalsDesc(C.Structure):   # ouster_hip_normals_desc
+    _fields_ = [("xyz", C.c_void_p), ("range", C.c_void_p), ("xyz2", C.c_void_p), ("range2", C.c_void_p),
+                ("normals", C.c_void_p), ("normals2", C.c_void_p), ("pixel_shift_by_row", C.c_void_p),
+                ("sensor_origins", C.c_void_p), ("poses", C.c_void_p), ("sensor_to_body", C.c_void_p),
+                ("xyz_rows", C.c_uint64), ("xyz2_rows", C.c_uint64),
+                ("n_frames", C.c_uint32), ("h", C.c_uint32), ("w", C.c_uint32), ("range2_h", C.c_uint32), ("range2_w", C.c_uint32),
+                ("n_origins", C.c_uint32), ("pixel_search_range", C.c_uint32), ("n_sensor_to_body", C.c_uint32), ("xyz_dtype", C.c_int32),
+                ("staggered_output", C.c_int32), ("min_angle_of_incidence_rad", C.c_double), ("target_distance_m", C.c_double)]
+
+
 # every symbol include/ouster_hip.h declares (checked by tests/test_abi.py)
 class AllocStats(C.Structure):
     """ouster_hip_alloc_stats (include/ouster_hip.h)"""
@@ -134,6 +149,8 @@ ABI_SYMBOLS = [
     "ouster_hip_pose_segments", "ouster_hip_pose_validate", "ouster_hip_interp_pose", "ouster_hip_interp_pose_host", "ouster_hip_interp_pose_pair_host",
     "ouster_hip_interp_pose_columns", "ouster_hip_interp_pose_pair_columns", "ouster_hip_transform",
     "ouster_hip_transform_host",
+    # algorithm::normals
+    "ouster_hip_normals_constants", "ouster_hip_normals", "ouster_hip_normals_host",
 ]
 
 _hip = None
@@ -258,6 +275,11 @@ def load_hip(private_path: Optional[str] = None):
         L.ouster_hip_interp_pose_pair_columns.argtypes = [vp, vp, vp, u32, u32, dbl, vp, dbl, vp, vp, vp]
         L.ouster_hip_transform.argtypes = [vp, vp, vp, vp, C.c_int, u64]
         L.ouster_hip_transform_host.argtypes = [vp, vp, vp, vp, C.c_int, u64]
+    if hasattr(L, "ouster_hip_normals"):   # absent only in older A/B builds loaded via OUSTER_HIP_SO
+        L.ouster_hip_normals_constants.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_int, C.c_double, C.c_uint32,
+                                                   C.POINTER(NormalsConsts)]
+        L.ouster_hip_normals.argtypes = [vp, C.POINTER(NormalsDesc)]
+        L.ouster_hip_normals_host.argtypes = [vp, C.POINTER(NormalsDesc)]
     if private_path is None:
         _hip = L
     return L

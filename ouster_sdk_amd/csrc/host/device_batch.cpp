@@ -87,6 +87,7 @@ DeviceFrameBatch::DeviceFrameBatch(const std::vector<SensorInfo>& sensors, uint3
     if (opt_.xyz)
         for (const auto& s : sensors) luts_.emplace_back(s, opt_.use_extrinsics);
     shifts_.assign(s0.format.pixel_shift_by_row.begin(), s0.format.pixel_shift_by_row.end());
+    for (const auto& s : sensors) sensor_to_body_.insert(sensor_to_body_.end(), s.sensor_to_body.m, s.sensor_to_body.m + 16);
     if (!opt_.destagger.empty() && shifts_.size() != h_)
         throw std::invalid_argument("image height does not match shifts size");
     d_packets_.resize(static_cast<size_t>(n_frames_) * slots_ * stride_);
@@ -676,6 +677,65 @@ void DeviceFrameBatch::download_image(const std::string& field, uint32_t frame, 
     const size_t bytes = static_cast<size_t>(h_) * w_ * 4;
     sync();
     it->second.download(host, bytes, bytes * frame);
+}
+
+void DeviceFrameBatch::normals(const NormalsOptions& o) {
+    ScopedContext on_my_context(ctx_);
+    const int n_ret = o.dual_return ? 2 : 1;
+    const std::string range_names[2] = {ChanField::RANGE, ChanField::RANGE2};
+    const void* range[2] = {nullptr, nullptr};
+    for (int k = 0; k < n_ret; ++k) {
+        const auto it = d_planes_.find(range_names[k]);
+        if (!opt_.xyz || xyz_field_[k] < 0 || it == d_planes_.end())
+            throw std::invalid_argument("DeviceFrameBatch::normals: the batch needs BatchOptions::xyz and the staggered plane of '" +
+                                        range_names[k] + "'");
+        range[k] = it->second.data();
+    }
+    if (shifts_.size() != h_) throw std::invalid_argument("image height does not match shifts size");
+    const size_t npx = static_cast<size_t>(h_) * w_;
+    ouster_hip_normals_desc d{};
+    d.xyz = d_xyz_[0].data();
+    d.range = static_cast<const uint32_t*>(range[0]);
+    d.xyz_rows = npx;
+    if (o.dual_return) {
+        d.xyz2 = d_xyz_[1].data();
+        d.range2 = static_cast<const uint32_t*>(range[1]);
+        d.xyz2_rows = npx, d.range2_h = h_, d.range2_w = w_;
+    }
+    d.n_frames = n_frames_, d.h = h_, d.w = w_;
+    d.pixel_shift_by_row = shifts_.data();
+    d.staggered_output = o.staggered_output ? 1 : 0;
+    d.xyz_dtype = opt_.xyz_f64 ? OUSTER_HIP_F64 : OUSTER_HIP_F32;
+    d.pixel_search_range = o.pixel_search_range;
+    d.min_angle_of_incidence_rad = o.min_angle_of_incidence_rad;
+    d.target_distance_m = o.target_distance_m;
+    if (opt_.xyz_world_frame) d.poses = poses_device();
+    if (opt_.use_extrinsics) {   // without it the cloud is the sensor's own: zeros, or the poses' translations
+        d.sensor_to_body = sensor_to_body_.data();
+        d.n_sensor_to_body = n_sensors_;
+    }
+    // refused before anything is allocated
+    ouster_hip_normals_consts unused;
+    if (ouster_hip_normals_constants(w_, h_, d.min_angle_of_incidence_rad, d.target_distance_m, 0, 0.0, 0, &unused) != OUSTER_HIP_OK)
+        throw std::runtime_error(ouster_hip_last_error());
+    for (int k = 0; k < n_ret; ++k)
+        if (d_normals_[k].size() != npx * 24 * n_frames_) d_normals_[k].resize(npx * 24 * n_frames_);
+    d.normals = static_cast<double*>(d_normals_[0].data());
+    if (o.dual_return) d.normals2 = static_cast<double*>(d_normals_[1].data());
+    if (ouster_hip_normals(default_ctx(), &d) != OUSTER_HIP_OK) throw std::runtime_error(ouster_hip_last_error());
+}
+
+double* DeviceFrameBatch::normals_device(int k) {
+    return k >= 0 && k < 2 && d_normals_[k].size() ? static_cast<double*>(d_normals_[k].data()) : nullptr;
+}
+
+void DeviceFrameBatch::download_normals(int k, uint32_t frame, double* host) {
+    ScopedContext on_my_context(ctx_);
+    if (frame >= n_frames_) throw std::out_of_range("DeviceFrameBatch: frame index");
+    if (!normals_device(k)) throw std::invalid_argument("DeviceFrameBatch::download_normals: normals() first");
+    const size_t bytes = static_cast<size_t>(h_) * w_ * 24;
+    sync();
+    d_normals_[k].download(host, bytes, bytes * frame);
 }
 
 void DeviceFrameBatch::upload_poses(uint32_t frame, const double* poses) {

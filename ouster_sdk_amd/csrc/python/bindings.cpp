@@ -15,6 +15,7 @@
 
 #include <pybind11/functional.h>
 
+#include "ouster/algorithm/normals.h"
 #include "ouster/core/frame_ops.h"
 #include "ouster/core/image_processing.h"
 #include "ouster/core/lidar_scan.h"
@@ -819,6 +820,52 @@ PYBIND11_MODULE(core, m) {
                 return std::move(out);
             },
             py::arg("points"), py::arg("pose"));
+    }
+
+    // normals: the call shapes of the reference's binding (python/src/cpp/algorithm: clouds (H, W, 3) or (H * W, 3), range (H, W),
+    // origins (W, 3)); results (H, W, 3), a pair for the dual form; the reference's messages as RuntimeError
+    {
+        namespace oa = ouster::sdk::algorithm;
+        using darr = py::array_t<double, py::array::c_style | py::array::forcecast>;
+        using uarr = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>;
+        auto cloud_rows = [](const darr& a) -> size_t {
+            if (a.ndim() < 2 || a.ndim() > 3 || a.shape(a.ndim() - 1) != 3) throw std::runtime_error("normals: xyz dimensions mismatch");
+            return static_cast<size_t>(a.size() / 3);
+        };
+        auto run = [cloud_rows](const darr& xyz, const uarr& range, const darr* xyz2, const uarr* range2, const darr& origins, size_t psr,
+                                double min_angle, double target) -> py::object {
+            if (range.ndim() != 2 || (range2 && range2->ndim() != 2)) throw py::type_error("normals: range must have shape (H, W)");
+            if (origins.ndim() != 2 || origins.shape(1) != 3)
+                throw py::type_error("normals(): incompatible function arguments: sensor_origins_xyz must have shape (W, 3)");
+            const size_t h = static_cast<size_t>(range.shape(0)), w = static_cast<size_t>(range.shape(1));
+            const std::vector<py::ssize_t> shape = {static_cast<py::ssize_t>(h), static_cast<py::ssize_t>(w), 3};
+            py::array_t<double> out(shape), out2(xyz2 ? shape : std::vector<py::ssize_t>{0, 0, 3});
+            static const double no_xyz = 0.0;
+            static const uint32_t no_range = 0;
+            oa::impl::normals_arrays(xyz.data(), cloud_rows(xyz), range.data(), h, w,
+                                     xyz2 ? (xyz2->size() ? xyz2->data() : &no_xyz) : nullptr, xyz2 ? cloud_rows(*xyz2) : 0,
+                                     range2 ? (range2->size() ? range2->data() : &no_range) : nullptr,
+                                     range2 ? static_cast<size_t>(range2->shape(0)) : 0, range2 ? static_cast<size_t>(range2->shape(1)) : 0,
+                                     origins.data(), static_cast<size_t>(origins.shape(0)), psr, min_angle, target, out.mutable_data(),
+                                     xyz2 ? out2.mutable_data() : nullptr);
+            if (xyz2) return py::make_tuple(out, out2);
+            return std::move(out);
+        };
+        m.def(
+            "normals",
+            [run](const darr& xyz, const uarr& range, const darr& origins, size_t psr, double min_angle, double target) {
+                return run(xyz, range, nullptr, nullptr, origins, psr, min_angle, target);
+            },
+            py::arg("xyz"), py::arg("range"), py::arg("sensor_origins_xyz"), py::arg("pixel_search_range") = 1,
+            py::arg("min_angle_of_incidence_rad") = oa::DEFAULT_MIN_ANGLE_INCIDENCE_RAD,
+            py::arg("target_distance_m") = oa::DEFAULT_TARGET_DISTANCE_METER);
+        m.def(
+            "normals",
+            [run](const darr& xyz, const uarr& range, const darr& xyz2, const uarr& range2, const darr& origins, size_t psr,
+                  double min_angle, double target) { return run(xyz, range, &xyz2, &range2, origins, psr, min_angle, target); },
+            py::arg("xyz"), py::arg("range"), py::arg("xyz2"), py::arg("range2"), py::arg("sensor_origins_xyz"),
+            py::arg("pixel_search_range") = 1, py::arg("min_angle_of_incidence_rad") = oa::DEFAULT_MIN_ANGLE_INCIDENCE_RAD,
+            py::arg("target_distance_m") = oa::DEFAULT_TARGET_DISTANCE_METER);
     }
 
     // extension over the reference's Python surface: the C++ dewarp(LidarFrame, XYZLut, min_range,
