@@ -363,7 +363,8 @@ int ouster_hip_range_gate(double min_range, double max_range, uint32_t* min_r, u
 #define OUSTER_HIP_OSF_PNG_RGB8 3    /* 24-bit values */
 #define OUSTER_HIP_OSF_PNG_RGBA8 4   /* 32-bit values */
 #define OUSTER_HIP_OSF_PNG_RGBA16 5  /* 64-bit values */
-#define OUSTER_HIP_OSF_ZPNG 6        /* src_pixel_bytes = channels * bytes per channel (1..8) */
+#define OUSTER_HIP_OSF_ZPNG 6        /* src_pixel_bytes = channels * bytes per channel (1..8); 3 and 4 are planar (colour planes,
+                                      * GB-RG), the other sizes interleaved; all of 1..8 are tested (tests/test_gpu_osf_unpack.py) */
 typedef struct ouster_hip_osf_plane {
     const void* src;          /* device */
     void* dst;                /* device, [h][w] elements of dst_elem_size bytes */

@@ -253,6 +253,28 @@ def decode_png_field(data: bytes, dtype, h: int, w: int) -> np.ndarray:
     return val.astype(dtype)
 
 
+def zpng_unfilter(residuals, h: int, w: int, pixel_bytes: int) -> np.ndarray:
+    """UnpackAndUnfilter<N> (thirdparty/zpng/zpng.cpp:101-352) on the zstd-decompressed body of a ZPNG image: the pixel bytes,
+    uint8 [h, w, pixel_bytes], for every pixel size the header allows (1..8).  3- and 4-byte pixels are stored as colour
+    planes under the GB-RG transform; every other size interleaved; then per row and byte lane a running sum mod 256."""
+    if not 1 <= pixel_bytes <= 8:
+        raise ValueError("ZPNG pixels are 1..8 bytes")
+    body = np.frombuffer(bytes(residuals), np.uint8)
+    if body.size != h * w * pixel_bytes:
+        raise ValueError("ZPNG body size mismatch")
+    if pixel_bytes in (3, 4):     # colour planes + GB-RG transform, then the left delta
+        planes = body.reshape(pixel_bytes, h, w).astype(np.int64)
+        y, u, v = planes[0], planes[1], planes[2]
+        B = y
+        G = (u + B) & 0xFF
+        r0 = (G - v) & 0xFF
+        chans = [r0, G, B] + ([planes[3]] if pixel_bytes == 4 else [])
+        out = np.stack([np.cumsum(c, axis=1) & 0xFF for c in chans], axis=-1).astype(np.uint8)
+    else:
+        out = (np.cumsum(body.reshape(h, w, pixel_bytes).astype(np.int64), axis=1) & 0xFF).astype(np.uint8)
+    return np.ascontiguousarray(out).reshape(h, w, pixel_bytes)
+
+
 def decode_zpng_field(data: bytes, dtype, h: int, w: int) -> Optional[np.ndarray]:
     if len(data) < 8:
         return None
@@ -262,18 +284,8 @@ def decode_zpng_field(data: bytes, dtype, h: int, w: int) -> Optional[np.ndarray
     pixel_bytes = ch * bpc
     if (zw, zh) != (w, h) or pixel_bytes != np.dtype(dtype).itemsize:
         raise ValueError("Invalid allocation")
-    body = np.frombuffer(zstd_decompress(data[8:], w * h * pixel_bytes), np.uint8)
-    if pixel_bytes in (3, 4):     # colour planes + GB-RG transform, then the left delta
-        planes = body.reshape(pixel_bytes, h, w).astype(np.int32)
-        y, u, v = planes[0], planes[1], planes[2]
-        B = y
-        G = (u + B) & 0xFF
-        r0 = (G - v) & 0xFF
-        chans = [r0, G, B] + ([planes[3]] if pixel_bytes == 4 else [])
-        out = np.stack([np.cumsum(c, axis=1) & 0xFF for c in chans], axis=-1).astype(np.uint8)
-    else:
-        out = (np.cumsum(body.reshape(h, w, pixel_bytes).astype(np.int32), axis=1) & 0xFF).astype(np.uint8)
-    return np.ascontiguousarray(out).reshape(h, w * pixel_bytes).view(dtype).reshape(h, w)
+    out = zpng_unfilter(zstd_decompress(data[8:], w * h * pixel_bytes), h, w, pixel_bytes)
+    return out.reshape(h, w * pixel_bytes).view(dtype).reshape(h, w)
 
 
 def stagger(img: np.ndarray, shifts) -> np.ndarray:

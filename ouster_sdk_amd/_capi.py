@@ -204,6 +204,8 @@ def load_hip(private_path: Optional[str] = None):
     L.ouster_hip_destagger.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp,
                                        C.c_uint32, C.c_int, C.c_uint32]
     L.ouster_hip_cartesian.argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint32]
+    if hasattr(L, "ouster_hip_osf_unpack"):   # absent only in older A/B builds loaded via OUSTER_HIP_SO
+        L.ouster_hip_osf_unpack.argtypes = [vp, C.POINTER(OsfPlane), C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.ouster_hip_dewarp.argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]
     L.ouster_hip_dewarp_frames.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_double,
                                            C.c_double, C.c_int, vp, vp, vp, vp, C.c_uint64, vp]

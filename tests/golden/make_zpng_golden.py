@@ -2,7 +2,8 @@
 """Writes tests/golden/osf/zpng_ref_vectors.json: field planes compressed by the REFERENCE's own ZPNG codec
 (oracle/_ref/libzpng_ref.so = /root/reference/thirdparty/zpng/zpng.cpp, built by oracle/Makefile) in the
 layouts the reference's OSF writer uses (zpng_lidarframe_encoder.cpp:52-73), with the sha256 of the plane
-each must decode to.  Run in the build container (needs /root/reference for the build); the vectors
+each must decode to; and, with their own shape fields, planes of the pixel sizes that writer never produces (3, 5, 6, 7 bytes)
+with the sha256 of their pixel bytes.  Run in the build container (needs /root/reference for the build); the vectors
 travel, the reference does not."""
 import base64
 import hashlib
@@ -32,6 +33,23 @@ def planes():
     yield "ones_uint16", np.full((H, W), 0xFFFF, np.uint16)
 
 
+# pixel sizes the OSF writer never produces but the codec's header allows (zpng.cpp:426-452): their own, ragged shape
+PH, PW = 3, 70
+PIXEL_LAYOUTS = {3: (3, 1), 5: (5, 1), 6: (3, 2), 7: (7, 1)}   # pixel bytes -> (channels, bytes per channel)
+
+
+def pixel_planes():
+    """name, uint8 [PH, PW * pb] pixel bytes, channels, bytes per channel"""
+    rng = np.random.default_rng(0x5eed + 1)
+    col = np.arange(PW, dtype=np.int64)[None, :, None]
+    row = np.arange(PH, dtype=np.int64)[:, None, None]
+    for pb, (ch, bpc) in PIXEL_LAYOUTS.items():
+        yield f"random_{pb}B", rng.integers(0, 256, (PH, PW * pb), dtype=np.uint8), ch, bpc
+        lane = np.arange(pb, dtype=np.int64)[None, None, :]
+        smooth = (row * 37 + col * (3 + lane) + (row * col) % 5 + lane * 50) & 0xFF   # small left deltas in every byte lane
+        yield f"smooth_{pb}B", smooth.astype(np.uint8).reshape(PH, PW * pb), ch, bpc
+
+
 def main():
     if not zpng_ref.available():
         sys.exit("oracle/_ref/libzpng_ref.so missing: run `make -C oracle` where /root/reference exists")
@@ -42,9 +60,17 @@ def main():
         assert (w, h) == (W, H) and px == p.tobytes(), name
         out["vectors"][name] = {"dtype": p.dtype.name, "zpng": base64.b64encode(blob).decode(),
                                 "sha256": hashlib.sha256(p.tobytes()).hexdigest()}
+    out["pixel_size_vectors"] = {}
+    for name, px, ch, bpc in pixel_planes():
+        blob = zpng_ref.compress_pixels(px, ch, bpc)
+        back, w, h, c, b = zpng_ref.decompress(blob)
+        assert (w, h, c, b) == (PW, PH, ch, bpc) and back == px.tobytes(), name
+        out["pixel_size_vectors"][name] = {"h": PH, "w": PW, "channels": ch, "bytes_per_channel": bpc,
+                                           "zpng": base64.b64encode(blob).decode(),
+                                           "sha256": hashlib.sha256(px.tobytes()).hexdigest()}
     path = os.path.join(HERE, "osf", "zpng_ref_vectors.json")
     json.dump(out, open(path, "w"), indent=1)
-    print("wrote", path, {k: len(v["zpng"]) for k, v in out["vectors"].items()})
+    print("wrote", path, {k: len(v["zpng"]) for k, v in {**out["vectors"], **out["pixel_size_vectors"]}.items()})
 
 
 if __name__ == "__main__":

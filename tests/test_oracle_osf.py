@@ -160,15 +160,112 @@ def _zpng_vectors():
                             for k, v in d["vectors"].items()}
 
 
+def _zpng_pixel_size_vectors():
+    """The vectors of pixel sizes the OSF writer never produces: name -> (h, w, channels, bytes per channel, blob, sha256)."""
+    import base64
+    d = json.load(open(os.path.join(OSF_DIR, "zpng_ref_vectors.json")))
+    return {k: (v["h"], v["w"], v["channels"], v["bytes_per_channel"], base64.b64decode(v["zpng"]), v["sha256"])
+            for k, v in d["pixel_size_vectors"].items()}
+
+
 def test_zpng_oracle_decodes_the_reference_codecs_vectors():
     """Committed vectors: planes compressed by the reference's ZPNG_Compress in the layouts its OSF writer
-    uses (u8: 1x1 B, u16: 1x2 B, u32: 4x1 B with the colour transform, u64: 4x2 B)."""
+    uses (u8: 1x1 B, u16: 1x2 B, u32: 4x1 B with the colour transform, u64: 4x2 B), and -- with their own ragged
+    shape -- in the pixel sizes it never writes (3 B: the planar case without a fourth plane; 5, 6, 7 B)."""
+    import struct
     from oracle import osf_oracle as Z
     h, w, vec = _zpng_vectors()
     assert len(vec) >= 10
     for name, (dt, blob, sha) in vec.items():
         got = Z.decode_zpng_field(blob, dt, h, w)
         assert got is not None and got.dtype == dt and _sha(got) == sha, name
+    more = _zpng_pixel_size_vectors()
+    assert sorted({c * b for (_, _, c, b, _, _) in more.values()}) == [3, 5, 6, 7] and len(more) == 8
+    for name, (vh, vw, ch, bpc, blob, sha) in more.items():
+        assert struct.unpack_from("<HHHBB", blob, 0) == (0xFBF8, vw, vh, ch, bpc), name
+        assert vh > 1 and vw % 64 != 0
+        pb = ch * bpc
+        got = Z.zpng_unfilter(Z.zstd_decompress(blob[8:], vh * vw * pb), vh, vw, pb)
+        assert got.shape == (vh, vw, pb) and got.dtype == np.uint8 and _sha(got) == sha, name
+
+
+# ---------------------------------------------------------------------------------------------
+# every pixel size the ZPNG header allows (1..8 bytes; zpng.cpp:426-452), at ragged shapes
+# ---------------------------------------------------------------------------------------------
+ZPNG_SHAPES = [(1, 1), (3, 5), (2, 257), (5, 1000)]
+_NO_ZPNG_REF = "oracle/_ref/libzpng_ref.so not built (no /root/reference at build time)"
+
+
+def _zpng_cases(pb):
+    """(h, w, pixels uint8 [h, w * pb]) per shape: random bytes, every third column small so that deltas of both signs and
+    sizes occur in every byte lane."""
+    rng = np.random.default_rng(9000 + pb)
+    for h, w in ZPNG_SHAPES:
+        px = rng.integers(0, 256, (h, w, pb), dtype=np.uint8)
+        px[:, ::3] >>= 5
+        yield h, w, px.reshape(h, w * pb)
+
+
+@pytest.mark.parametrize("pb", range(1, 9))
+def test_zpng_unfilter_inverts_the_encoder_model(pb):
+    """oracle.zpng_unfilter (the decoder side) gives back what tests/zpng_model.residuals (the encoder side) was given, for
+    1..8-byte pixels; through the header + zstd frame of zpng_model.encode where the pixel is a field element."""
+    import zpng_model as M
+    from oracle import osf_oracle as Z
+    ch, bpc = M.LAYOUTS[pb]
+    assert ch * bpc == pb
+    for h, w, px in _zpng_cases(pb):
+        res = M.residuals(px, h, w, pb)
+        assert len(res) == h * w * pb
+        got = Z.zpng_unfilter(res, h, w, pb)
+        assert got.dtype == np.uint8 and got.shape == (h, w, pb) and got.tobytes() == px.tobytes(), (pb, h, w)
+        blob = M.encode(px, h, w, ch, bpc)
+        assert Z.zstd_decompress(blob[8:], len(res)) == res
+        if pb in (1, 2, 4, 8):
+            dt = np.dtype("<u%d" % pb)
+            assert Z.decode_zpng_field(blob, dt, h, w).tobytes() == px.tobytes(), (pb, h, w)
+        else:   # no field element of that size: decode_zpng_field keeps refusing it
+            with pytest.raises(ValueError, match="Invalid allocation"):
+                Z.decode_zpng_field(blob, np.uint32 if pb == 3 else np.uint64, h, w)
+    with pytest.raises(ValueError):
+        Z.zpng_unfilter(b"\0" * 9, 1, 1, 9)
+    with pytest.raises(ValueError):
+        Z.zpng_unfilter(b"\0" * (pb + 1), 1, 1, pb)
+
+
+@pytest.mark.parametrize("pb", range(1, 9))
+def test_zpng_encoder_model_is_decoded_by_the_reference(pb):
+    """ZPNG_Decompress of the reference's zpng.cpp gives the pixels back from zpng_model.encode."""
+    import zpng_ref
+    if not zpng_ref.available():
+        pytest.skip(_NO_ZPNG_REF)
+    import zpng_model as M
+    ch, bpc = M.LAYOUTS[pb]
+    for h, w, px in _zpng_cases(pb):
+        back, zw, zh, c, b = zpng_ref.decompress(M.encode(px, h, w, ch, bpc))
+        assert (zw, zh, c, b) == (w, h, ch, bpc) and back == px.tobytes(), (pb, h, w)
+
+
+@pytest.mark.parametrize("pb", range(1, 9))
+def test_zpng_encoder_model_equals_the_reference_encoder(pb):
+    """The zstd-decompressed body of ZPNG_Compress's output is zpng_model.residuals byte for byte, and the oracle decodes
+    what ZPNG_Compress wrote."""
+    import struct
+    import zpng_ref
+    if not zpng_ref.available():
+        pytest.skip(_NO_ZPNG_REF)
+    import zpng_model as M
+    from oracle import osf_oracle as Z
+    ch, bpc = M.LAYOUTS[pb]
+    assert zpng_ref.ALL_LAYOUTS == M.LAYOUTS
+    for h, w, px in _zpng_cases(pb):
+        blob = zpng_ref.compress_pixels(px, ch, bpc)
+        assert struct.unpack_from("<HHHBB", blob, 0) == (M.MAGIC, w, h, ch, bpc)
+        body = Z.zstd_decompress(blob[8:], h * w * pb)
+        assert body == M.residuals(px, h, w, pb), (pb, h, w)
+        assert Z.zpng_unfilter(body, h, w, pb).tobytes() == px.tobytes(), (pb, h, w)
+        if pb in (1, 2, 4, 8):
+            assert Z.decode_zpng_field(blob, np.dtype("<u%d" % pb), h, w).tobytes() == px.tobytes(), (pb, h, w)
 
 
 def test_zpng_oracle_matches_the_reference_decoder():

@@ -40,21 +40,31 @@ def _load():
 
 # how zpng_lidarframe_encoder.cpp:52-73 presents a field plane to the codec
 LAYOUT = {1: (1, 1), 2: (1, 2), 4: (4, 1), 8: (4, 2)}   # itemsize -> (channels, bytes per channel)
+# one layout for every pixel size the header allows: pixel bytes -> (channels, bytes per channel)
+ALL_LAYOUTS = {1: (1, 1), 2: (1, 2), 3: (3, 1), 4: (4, 1), 5: (5, 1), 6: (3, 2), 7: (7, 1), 8: (4, 2)}
 
 
 def compress(plane: np.ndarray) -> bytes:
     """ZPNG_Compress of an H x W plane of u8 / u16 / u32 / u64, laid out like the reference's OSF writer."""
-    lib = _load()
     plane = np.ascontiguousarray(plane)
     h, w = plane.shape
-    ch, bpc = LAYOUT[plane.dtype.itemsize]
-    raw = plane.view(np.uint8).reshape(-1)
+    return compress_pixels(plane.view(np.uint8).reshape(h, -1), *LAYOUT[plane.dtype.itemsize])
+
+
+def compress_pixels(pixels: np.ndarray, channels: int, bytes_per_channel: int) -> bytes:
+    """ZPNG_Compress of uint8 [h, w * channels * bytes_per_channel] pixel bytes in any layout the codec takes (1..8 bytes a pixel)."""
+    lib = _load()
+    pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+    h, stride = pixels.shape
+    pb = channels * bytes_per_channel
+    assert pb and stride % pb == 0
+    raw = pixels.reshape(-1)
     img = _ImageData()
     img.Buffer.Data = raw.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte))
     img.Buffer.Bytes = raw.size
-    img.BytesPerChannel, img.Channels = bpc, ch
-    img.WidthPixels, img.HeightPixels = w, h
-    img.StrideBytes = w * ch * bpc
+    img.BytesPerChannel, img.Channels = bytes_per_channel, channels
+    img.WidthPixels, img.HeightPixels = stride // pb, h
+    img.StrideBytes = stride
     out = lib.ZPNG_Compress(ctypes.byref(img))
     if not out.Data:
         raise RuntimeError("ZPNG_Compress failed")
