@@ -15,6 +15,7 @@
 
 #include "ouster/core/image_processing.h"
 #include "ouster/core/lidar_frame.h"
+#include "ouster/core/voxel_hash_map.h"
 #include "ouster/core/xyzlut.h"
 #include "ouster/hip/context.h"
 #include "ouster/hip/device_buffer.h"
@@ -90,6 +91,14 @@ struct NormalsOptions {
     double target_distance_m = 0.025;
     bool dual_return = false;        ///< both returns in one launch, each a source of neighbour candidates for the other
     bool staggered_output = false;   ///< normal i belongs to point i of xyz_device(); false: the reference's destaggered layout
+};
+
+/** Parameters of DeviceFrameBatch::voxel_downsample: those of core::voxel_downsample_3d (core/voxel_hash_map.h), except that the
+ *  default strategy is AVERAGE_POINT. */
+struct VoxelOptions {
+    core::VoxelDownsampleStrategy strategy = core::VoxelDownsampleStrategy::AVERAGE_POINT;
+    size_t max_points_per_voxel = 1;   ///< FIRST_N_POINT / RANDOM; more than 1 is host code and refused on a resident cloud
+    size_t min_pts_threshold = 1;      ///< AVERAGE_POINT
 };
 
 class DeviceFrameBatch {
@@ -232,6 +241,29 @@ class DeviceFrameBatch {
      *  @throw std::invalid_argument before normals() has made that return's normals */
     void download_normals(int return_index, uint32_t frame, double* host);
 
+    /** core::voxel_downsample_3d (core/voxel_hash_map.h; csrc/k_voxel.hip) over the result of the last dewarp(): the world-frame
+     *  points of all frames form one cloud (a float batch's points are widened, which is exact).  The rows, double (M, 3) in
+     *  first-seen order, stay in HBM (voxels_device(), voxel_count()) and equal tests/voxel_model.py on download_dewarped()'s
+     *  points bit for bit.  Synchronous, on the batch's context.  Returns M.
+     *  @throw std::invalid_argument before the first dewarp(), and with the reference's messages for the parameters and
+     *         "voxel_downsample: point outside the int32 voxel grid"
+     *  @throw std::runtime_error for FIRST_N_POINT / RANDOM with max_points_per_voxel > 1 (host code only) */
+    uint64_t voxel_downsample(double voxel_size, const VoxelOptions& options = VoxelOptions());
+    /** algorithm::voxel_downsample_with_normals (algorithm/voxel_downsample.h) over xyz_device(return_index) and the
+     *  normals_device(return_index) of a previous normals() made with NormalsOptions::staggered_output, so that normal i belongs to
+     *  point i.  Pixels without range have a zero normal and take no part.  Results as above, with voxel_normals_device().
+     *  @throw std::invalid_argument when normals() has not made that return's normals, or made them in the destaggered layout */
+    uint64_t voxel_downsample_with_normals(double voxel_size, int return_index = 0);
+    /** Rows of the last voxel_downsample() / voxel_downsample_with_normals(): double [voxel_count()][3]; nullptr before the first
+     *  call and after a call that threw (it leaves no result: voxel_count() is 0 and download_voxels throws). */
+    double* voxels_device();
+    /** Unit normals of the last voxel_downsample_with_normals(); nullptr when the last call was voxel_downsample(). */
+    double* voxel_normals_device();
+    uint64_t voxel_count() const { return vox_count_; }
+    /** Copy the rows to the host (voxel_count() x 3 doubles each; null pointers are skipped; synchronous).
+     *  @throw std::invalid_argument before the first call, or for normals when the last call made none */
+    void download_voxels(double* points, double* normals);
+
     /** Per-column body_to_world poses of one frame (w x 16 doubles, row-major 4x4 each; identity
      *  until set), the input of dewarp(). */
     void upload_poses(uint32_t frame, const double* poses_w_by_16);
@@ -301,6 +333,11 @@ class DeviceFrameBatch {
     std::vector<uint64_t> dw_offsets_;
     std::vector<double> sensor_to_body_;   // [sensors][16], row-major
     DeviceBuffer d_normals_[2];            // normals(): f64 [n_frames][h * w][3] per return, made on first use
+    bool normals_staggered_[2] = {false, false};   // the layout the last normals() wrote that return in
+    DeviceBuffer d_vox_pts_, d_vox_nrm_;   // voxel_downsample*(): f64 [points in][3], the first vox_count_ rows are the result
+    uint64_t vox_count_ = 0;
+    bool vox_made_ = false, vox_normals_ = false;
+    uint64_t voxel_run_(const void* points, const double* normals, uint64_t n, double voxel_size, const VoxelOptions& o);
     bool dw_prov_ = false;
 };
 

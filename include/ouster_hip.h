@@ -689,6 +689,63 @@ int ouster_hip_normals(ouster_hip_ctx* ctx, const ouster_hip_normals_desc* desc)
 /* The same with every array in host memory (pool memory in place, anything else through the context's grow-only scratch). */
 int ouster_hip_normals_host(ouster_hip_ctx* ctx, const ouster_hip_normals_desc* desc);
 
+/* ---- voxel down-sampling ---------------------------------------------------------- */
+/* Replaces ouster::sdk::core::voxel_downsample_3d / voxel_downsample_xd (ouster_core/src/voxel_hash_map.cpp:312-393) and
+ * ouster::sdk::algorithm::voxel_downsample_with_normals (ouster_algorithm/src/voxel_downsample.cpp).  The voxel of a point is
+ * int(floor(p * (1.0 / voxel_size))) per axis, over the first three columns.  The result equals a float64 restatement of the
+ * reference (tests/voxel_model.py) bit for bit: sums are left folds over a voxel's points in input order, never atomics.
+ * Rows come in first-seen order (voxels by the input index of their first contributing point; a voxel's points, where a strategy
+ * keeps several, consecutively in admission order); the reference's order is its hash map's iteration order.
+ * On the GPU: k_voxel_keys, k_voxel_insert (open addressing over point indices, the smallest index of a voxel wins its slot), a scan
+ * and a stable radix sort by voxel id (rocPRIM), k_voxel_reduce and k_voxel_write (k_voxel.hip).  Every intermediate lives in a
+ * grow-only workspace of the context; a call ends with one read-back of the row count and a status word.
+ * Refused with OUSTER_HIP_ERR_INVALID_ARGUMENT before anything touches the GPU: "max_points_per_voxel must be greater than 0",
+ * then "voxel_size must be greater than 0" (also a non-finite one), cols < 3 ("voxel_downsample_xd: frame must be Nx>=3 (x,y,z +
+ * optional attributes)"); with normals: cols != 3 ("voxel_downsample_with_normals expects Nx3 inputs") and
+ * "voxel_downsample_with_normals voxel_size must be > 0".  Refused by the kernels (same code, no output row written): a
+ * non-finite coordinate among the first three columns, or one whose floor(p / voxel_size) no int32 holds, "voxel_downsample:
+ * point outside the int32 voxel grid".  With normals, rows with a non-finite point or normal coordinate or a normal no longer
+ * than 1e-12 are skipped, as in the reference, and only the rows that remain are held to the grid.
+ * More than 2^30 points: OUSTER_HIP_ERR_UNSUPPORTED. */
+#define OUSTER_HIP_VOXEL_FIRST_N_POINT 0   /* the values of core::VoxelDownsampleStrategy */
+#define OUSTER_HIP_VOXEL_AVERAGE_POINT 1
+#define OUSTER_HIP_VOXEL_RANDOM 2
+typedef struct ouster_hip_voxel_desc {
+    const void* points;            /* [n][row_stride] of dtype; the first `cols` elements of a row take part */
+    const double* normals;         /* [n][3] f64, dense; not NULL selects the with-normals form (cols == 3; strategy,
+                                      max_points_per_voxel and min_pts_threshold are not read) */
+    double* out;                   /* [out_capacity][cols] f64, dense */
+    double* out_normals;           /* [out_capacity][3] f64: the with-normals form's unit normals */
+    uint64_t n;                    /* points; 0: *n_out = 0 and nothing else is looked at (without normals) */
+    uint64_t out_capacity;         /* rows `out` (and `out_normals`) can hold */
+    uint64_t row_stride;           /* elements from one input row to the next; 0: dense (cols) */
+    uint64_t max_points_per_voxel; /* FIRST_N_POINT, RANDOM: points a voxel keeps */
+    uint64_t min_pts_threshold;    /* AVERAGE_POINT: a voxel with fewer points is not emitted */
+    double voxel_size;
+    uint32_t cols;                 /* 3 + attribute columns */
+    int32_t dtype;                 /* of points: OUSTER_HIP_F32 (widened on load, exact) / OUSTER_HIP_F64 */
+    int32_t strategy;              /* OUSTER_HIP_VOXEL_* */
+    uint32_t table_log2;           /* 0: the hash table gets the smallest power of two >= 2 n slots; otherwise 2^table_log2 slots,
+                                      which must exceed n (and table_log2 <= 31), else INVALID_ARGUMENT.  Changes no result */
+} ouster_hip_voxel_desc;
+/* Every array in device memory.  Synchronous.  *n_out: rows written.  If the result needs more than out_capacity rows, nothing is
+ * written, *n_out is the count needed and the call returns OUSTER_HIP_ERR_INVALID_ARGUMENT.  FIRST_N_POINT and RANDOM with
+ * max_points_per_voxel > 1 are sequential by nature: OUSTER_HIP_ERR_UNSUPPORTED here, host code in the _host form. */
+int ouster_hip_voxel_downsample(ouster_hip_ctx* ctx, const ouster_hip_voxel_desc* desc, uint64_t* n_out);
+/* The same with every array in host memory (pool memory in place, anything else through the context's grow-only scratch).  The two
+ * combinations the GPU does not take run ouster_hip_voxel_downsample_ref. */
+int ouster_hip_voxel_downsample_host(ouster_hip_ctx* ctx, const ouster_hip_voxel_desc* desc, uint64_t* n_out);
+/* The plain C++ restatement on host arrays: every strategy, the same validation, refusals, row order and out_capacity rule, one
+ * core, no GPU.  table_log2 is not read. */
+int ouster_hip_voxel_downsample_ref(const ouster_hip_voxel_desc* desc, uint64_t* n_out);
+/* Times of the phases of a call, for measurement (tools/ab/voxel_bench.py).  on != 0: every later ouster_hip_voxel_downsample
+ * (and _host) on this context records an event around each phase; 0: none (the default; events cost the stream a few us each). */
+#define OUSTER_HIP_VOXEL_PHASES 7   /* table reset + keys, insert, ids (first + scan + ids), sort, segments, reduce (gather + fold +
+                                       scan; empty for the row-copy forms), write */
+int ouster_hip_voxel_timing(ouster_hip_ctx* ctx, int on);
+/* ms[OUSTER_HIP_VOXEL_PHASES] of the last timed call that reached the GPU; INVALID_ARGUMENT when there was none. */
+int ouster_hip_voxel_phase_ms(ouster_hip_ctx* ctx, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

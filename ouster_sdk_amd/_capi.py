@@ -103,6 +103,17 @@ FOPS_TYPES = {"uint8": U8, "uint16": U16, "uint32": U32, "uint64": U64, "int8": 
               "int64": I64, "float32": F32, "float64": F64}
 
 
+VOXEL_PHASES = ("keys", "insert", "ids", "sort", "segments", "reduce", "write")   # OUSTER_HIP_VOXEL_PHASES
+VOXEL_FIRST_N_POINT, VOXEL_AVERAGE_POINT, VOXEL_RANDOM = 0, 1, 2   # OUSTER_HIP_VOXEL_*: core::VoxelDownsampleStrategy
+
+
+class VoxelDesc(C.Structure):   # ouster_hip_voxel_desc
+    _fields_ = [("points", C.c_void_p), ("normals", C.c_void_p), ("out", C.c_void_p), ("out_normals", C.c_void_p),
+                ("n", C.c_uint64), ("out_capacity", C.c_uint64), ("row_stride", C.c_uint64),
+                ("max_points_per_voxel", C.c_uint64), ("min_pts_threshold", C.c_uint64), ("voxel_size", C.c_double),
+                ("cols", C.c_uint32), ("dtype", C.c_int32), ("strategy", C.c_int32), ("table_log2", C.c_uint32)]
+
+
 class NormalsConsts(C.Structure):   # ouster_hip_normals_consts
     _fields_ = [("px_res_h", C.c_double), ("px_res_v", C.c_double), ("tan_safe", C.c_double), ("target_sq", C.c_double),
                 ("subtent", C.c_double)]
@@ -151,6 +162,9 @@ ABI_SYMBOLS = [
     "ouster_hip_transform_host",
     # algorithm::normals
     "ouster_hip_normals_constants", "ouster_hip_normals", "ouster_hip_normals_host",
+    # voxel down-sampling
+    "ouster_hip_voxel_downsample", "ouster_hip_voxel_downsample_host", "ouster_hip_voxel_downsample_ref",
+    "ouster_hip_voxel_timing", "ouster_hip_voxel_phase_ms",
 ]
 
 _hip = None
@@ -282,6 +296,12 @@ def load_hip(private_path: Optional[str] = None):
                                                    C.POINTER(NormalsConsts)]
         L.ouster_hip_normals.argtypes = [vp, C.POINTER(NormalsDesc)]
         L.ouster_hip_normals_host.argtypes = [vp, C.POINTER(NormalsDesc)]
+    if hasattr(L, "ouster_hip_voxel_downsample"):
+        L.ouster_hip_voxel_downsample.argtypes = [vp, C.POINTER(VoxelDesc), C.POINTER(C.c_uint64)]
+        L.ouster_hip_voxel_downsample_host.argtypes = [vp, C.POINTER(VoxelDesc), C.POINTER(C.c_uint64)]
+        L.ouster_hip_voxel_downsample_ref.argtypes = [C.POINTER(VoxelDesc), C.POINTER(C.c_uint64)]
+        L.ouster_hip_voxel_timing.argtypes = [vp, C.c_int]
+        L.ouster_hip_voxel_phase_ms.argtypes = [vp, C.POINTER(C.c_float)]
     if private_path is None:
         _hip = L
     return L

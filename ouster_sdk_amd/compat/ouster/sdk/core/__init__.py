@@ -10,6 +10,11 @@ Packet = _core.LidarPacket      # the base class of the reference's packet types
 AutoExposure = _core.AutoExposure                        # ouster.sdk.core.AutoExposure / BeamUniformityCorrector of the reference
 BeamUniformityCorrector = _core.BeamUniformityCorrector
 SensorInfo = _core.SensorInfo   # SensorInfo(json_text) is a constructor of the C++ class (csrc/host/metadata.cpp)
+# voxel down-sampling on the GPU (csrc/k_voxel.hip): the reference's four names
+voxel_downsample_3d = _core.voxel_downsample_3d
+voxel_downsample_xd = _core.voxel_downsample_xd
+voxel_downsample = _core.voxel_downsample_xd
+VoxelDownsampleStrategy = _core.VoxelDownsampleStrategy
 
 
 class ChanField:

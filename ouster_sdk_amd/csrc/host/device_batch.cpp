@@ -723,6 +723,68 @@ void DeviceFrameBatch::normals(const NormalsOptions& o) {
     d.normals = static_cast<double*>(d_normals_[0].data());
     if (o.dual_return) d.normals2 = static_cast<double*>(d_normals_[1].data());
     if (ouster_hip_normals(default_ctx(), &d) != OUSTER_HIP_OK) throw std::runtime_error(ouster_hip_last_error());
+    for (int k = 0; k < n_ret; ++k) normals_staggered_[k] = o.staggered_output;
+}
+
+uint64_t DeviceFrameBatch::voxel_run_(const void* points, const double* normals, uint64_t n, double voxel_size, const VoxelOptions& o) {
+    ouster_hip_voxel_desc d{};
+    d.points = points, d.normals = normals;
+    d.n = n, d.out_capacity = n, d.cols = 3;
+    d.dtype = opt_.xyz_f64 ? OUSTER_HIP_F64 : OUSTER_HIP_F32;
+    d.voxel_size = voxel_size;
+    d.max_points_per_voxel = o.max_points_per_voxel, d.min_pts_threshold = o.min_pts_threshold;
+    d.strategy = static_cast<int32_t>(o.strategy);
+    // a call that throws leaves no result: the earlier one is given up before the buffers may move
+    vox_count_ = 0;
+    vox_made_ = vox_normals_ = false;
+    if (!normals && o.strategy != core::VoxelDownsampleStrategy::AVERAGE_POINT && o.max_points_per_voxel > 1)
+        throw std::runtime_error("DeviceFrameBatch::voxel_downsample: FIRST_N_POINT / RANDOM with max_points_per_voxel > 1 are "
+                                 "sequential host code (core::voxel_downsample_3d on downloaded points)");
+    uint64_t n_out = 0;
+    if (n) {
+        if (d_vox_pts_.size() < n * 24) d_vox_pts_.resize(n * 24);
+        if (normals && d_vox_nrm_.size() < n * 24) d_vox_nrm_.resize(n * 24);
+        d.out = static_cast<double*>(d_vox_pts_.data());
+        d.out_normals = normals ? static_cast<double*>(d_vox_nrm_.data()) : nullptr;
+    }
+    // n == 0 goes through the call as well: it returns no rows before it looks at anything else, as the reference does
+    const int rc = ouster_hip_voxel_downsample(default_ctx(), &d, &n_out);
+    if (rc == OUSTER_HIP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(ouster_hip_last_error());
+    if (rc != OUSTER_HIP_OK) throw std::runtime_error(ouster_hip_last_error());
+    vox_count_ = n_out;
+    vox_made_ = true, vox_normals_ = normals != nullptr;
+    return n_out;
+}
+
+uint64_t DeviceFrameBatch::voxel_downsample(double voxel_size, const VoxelOptions& o) {
+    ScopedContext on_my_context(ctx_);
+    if (dw_offsets_.empty()) throw std::invalid_argument("DeviceFrameBatch::voxel_downsample: dewarp() first");
+    return voxel_run_(d_dw_pts_.data(), nullptr, dw_offsets_.back(), voxel_size, o);
+}
+
+uint64_t DeviceFrameBatch::voxel_downsample_with_normals(double voxel_size, int k) {
+    ScopedContext on_my_context(ctx_);
+    if (!normals_device(k)) throw std::invalid_argument("DeviceFrameBatch::voxel_downsample_with_normals: normals() first");
+    if (!normals_staggered_[k])
+        throw std::invalid_argument("DeviceFrameBatch::voxel_downsample_with_normals: normals() must run with staggered_output, "
+                                    "so that normal i belongs to point i");
+    return voxel_run_(d_xyz_[k].data(), normals_device(k), static_cast<uint64_t>(n_frames_) * h_ * w_, voxel_size, VoxelOptions());
+}
+
+double* DeviceFrameBatch::voxels_device() { return vox_made_ ? static_cast<double*>(d_vox_pts_.data()) : nullptr; }
+
+double* DeviceFrameBatch::voxel_normals_device() {
+    return vox_made_ && vox_normals_ ? static_cast<double*>(d_vox_nrm_.data()) : nullptr;
+}
+
+void DeviceFrameBatch::download_voxels(double* points, double* normals) {
+    ScopedContext on_my_context(ctx_);
+    if (!vox_made_) throw std::invalid_argument("DeviceFrameBatch::download_voxels: voxel_downsample() first");
+    if (normals && !vox_normals_)
+        throw std::invalid_argument("DeviceFrameBatch::download_voxels: the last call was voxel_downsample(), which makes no normals");
+    if (!vox_count_) return;
+    if (points) d_vox_pts_.download(points, vox_count_ * 24);
+    if (normals) d_vox_nrm_.download(normals, vox_count_ * 24);
 }
 
 double* DeviceFrameBatch::normals_device(int k) {

@@ -23,6 +23,7 @@
 #include "k_image.h"
 #include "k_normals.h"
 #include "k_pose.h"
+#include "k_voxel.h"
 #include "ouster_hip_dev.h"
 
 using namespace ouster_hip_dev;
@@ -106,6 +107,9 @@ struct ouster_hip_ctx {
     hipEvent_t fops_ev = nullptr;
     DevBuf fops_tables;                  // ouster_hip_frame_ops_*: shift tables reduced to [0, w) / row indices of the call in flight
     DevBuf normals_pairs;                // ouster_hip_normals: what k_normals_subtent leaves, 16 bytes per frame and return
+    bool voxel_timing = false, voxel_timed = false;   // ouster_hip_voxel_timing: events around the phases of a call
+    hipEvent_t voxel_ev[OUSTER_HIP_VOXEL_PHASES + 1] = {};
+    DevBuf voxel_ws;                     // ouster_hip_voxel_downsample: keys, table, ids, sorted indices, gathered rows, sort temporaries
     DevBuf user_scratch[8];              // ouster_hip_ctx_scratch: what the *_host calls and bindings stage through
     uint32_t resident_wgs = 512;         // 2 workgroups (80 KB LDS each) per CU
     uint32_t cus = 256;                  // compute units (k_decode_stream: one persistent workgroup each)
@@ -335,6 +339,9 @@ void ouster_hip_ctx_destroy(ouster_hip_ctx* c) {
     c->image_mask.release();
     c->fops_tables.release();
     c->normals_pairs.release();
+    c->voxel_ws.release();
+    for (hipEvent_t& e : c->voxel_ev)
+        if (e) (void)hipEventDestroy(e), e = nullptr;
     if (c->fops_ev) (void)hipEventDestroy(c->fops_ev);
     if (c->fops_pin) (void)hipHostFree(c->fops_pin);
     for (auto& b : c->user_scratch) b.release();
@@ -2320,6 +2327,142 @@ int ouster_hip_normals_host(ouster_hip_ctx* ctx, const ouster_hip_normals_desc* 
     if (dual) d.normals2 = (double*)hout.dev[1];
     rc = normals_device(ctx, &d);
     if (rc != OUSTER_HIP_OK) return rc;
+    return hout.finish(ctx, out.data());
+}
+
+// ---- voxel down-sampling (k_voxel.hip, host/voxel_util.cpp) ------------------------------------------
+namespace {
+// everything but the device: NULL / dtype / stride / table_log2; 1: nothing to do (n == 0)
+int voxel_validate_call(const ouster_hip_voxel_desc* d, uint64_t* n_out) {
+    if (!d || !n_out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    *n_out = 0;
+    if (d->n == 0 && !d->normals) return 1;
+    if (const char* msg = voxel_validate(d)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (d->dtype != OUSTER_HIP_F32 && d->dtype != OUSTER_HIP_F64) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
+    if (d->row_stride && d->row_stride < d->cols) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "row_stride is smaller than cols");
+    if (d->table_log2 && (d->table_log2 > 31 || (1ull << d->table_log2) <= d->n))
+        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "voxel_downsample: 2^table_log2 must exceed n (table_log2 <= 31)");
+    if (d->n == 0) return 1;
+    if (!d->points || (d->out_capacity && (!d->out || (d->normals && !d->out_normals)))) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
+    return OUSTER_HIP_OK;
+}
+
+// d: every array in device memory, validated, a form the GPU takes
+int voxel_device(ouster_hip_ctx* ctx, const ouster_hip_voxel_desc* d, uint64_t* n_out) {
+    if (d->n > VOXEL_MAX_POINTS) return fail(OUSTER_HIP_ERR_UNSUPPORTED, "voxel_downsample: more than 2^30 points");
+    HIP_TRY(hipSetDevice(ctx->device));
+    VoxelArgs a{};
+    a.points = d->points, a.normals = d->normals;
+    a.n = (uint32_t)d->n, a.cols = d->cols;
+    a.stride = d->row_stride ? d->row_stride : d->cols;
+    a.f32 = d->dtype == OUSTER_HIP_F32;
+    a.form = voxel_form(d);
+    a.inv = 1.0 / d->voxel_size;
+    a.min_pts = d->min_pts_threshold;
+    a.out = d->out, a.out_normals = d->out_normals, a.out_capacity = d->out_capacity;
+    uint32_t log2 = d->table_log2;
+    if (!log2)
+        for (log2 = 1; (1ull << log2) < 2 * d->n; ++log2) {}
+    a.table_mask = (uint32_t)((1ull << log2) - 1);
+    const bool folds = a.form == VOXEL_FORM_AVERAGE || a.form == VOXEL_FORM_NORMALS;
+    size_t temp_bytes = 0;
+    HIP_TRY(voxel_temp_bytes(a.n, &temp_bytes));
+    // the workspace, every piece 256-byte aligned
+    const size_t n = a.n;
+    size_t total = 0;
+    auto take = [&total](size_t bytes) {
+        const size_t at = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t o_hdr = take(sizeof(VoxelHeader)), o_keys = take(n * sizeof(VoxelKey)), o_table = take(((size_t)a.table_mask + 1) * 4),
+                 o_slot = take(n * 4), o_first = take(n * 4), o_first_id = take(n * 4), o_vid = take(n * 4), o_idx = take(n * 4),
+                 o_svid = take(n * 4), o_sidx = take(n * 4), o_begin = take(n * 4), o_end = take(n * 4),
+                 o_keep = take(folds ? n * 4 : 0), o_pos = take(folds ? n * 4 : 0),
+                 o_rows = take(folds ? n * 8 * (a.form == VOXEL_FORM_NORMALS ? 6 : a.cols) : 0), o_temp = take(temp_bytes);
+    if (ctx->voxel_ws.cap < total) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (ctx->voxel_ws.ensure(total)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (voxel workspace, %zu bytes)", total);
+    }
+    uint8_t* ws = (uint8_t*)ctx->voxel_ws.p;
+    a.hdr = (VoxelHeader*)(ws + o_hdr), a.keys = (VoxelKey*)(ws + o_keys), a.table = (int32_t*)(ws + o_table);
+    a.slot = (uint32_t*)(ws + o_slot), a.first = (uint32_t*)(ws + o_first), a.first_id = (uint32_t*)(ws + o_first_id);
+    a.vid = (uint32_t*)(ws + o_vid), a.idx = (uint32_t*)(ws + o_idx), a.svid = (uint32_t*)(ws + o_svid), a.sidx = (uint32_t*)(ws + o_sidx);
+    a.seg_begin = (uint32_t*)(ws + o_begin), a.seg_end = (uint32_t*)(ws + o_end);
+    a.keep = (uint32_t*)(ws + o_keep), a.pos = (uint32_t*)(ws + o_pos), a.rows = (double*)(ws + o_rows);
+    ctx->voxel_timed = false;
+    HIP_TRY(voxel_run(a, ws + o_temp, temp_bytes, ctx->stream, ctx->voxel_timing ? ctx->voxel_ev : nullptr));
+    VoxelHeader hdr{};
+    HIP_TRY(hipMemcpyAsync(&hdr, a.hdr, sizeof hdr, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->voxel_timed = ctx->voxel_timing;
+    if (hdr.status == VOXEL_STATUS_TABLE) return fail(OUSTER_HIP_ERR_RUNTIME, "voxel_downsample: hash table exhausted");
+    if (hdr.status) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", VOXEL_MSG_GRID);
+    *n_out = hdr.n_out;
+    if (hdr.n_out > d->out_capacity) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "voxel_downsample: out_capacity is too small");
+    return OUSTER_HIP_OK;
+}
+}  // namespace
+
+int ouster_hip_voxel_timing(ouster_hip_ctx* ctx, int on) {
+    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (on)
+        for (hipEvent_t& e : ctx->voxel_ev)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+    ctx->voxel_timing = on != 0;
+    ctx->voxel_timed = false;
+    return OUSTER_HIP_OK;
+}
+
+int ouster_hip_voxel_phase_ms(ouster_hip_ctx* ctx, float* ms) {
+    if (!ctx || !ms) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!ctx->voxel_timed) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "voxel_downsample: no timed call (ouster_hip_voxel_timing)");
+    for (int k = 0; k < OUSTER_HIP_VOXEL_PHASES; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], ctx->voxel_ev[k], ctx->voxel_ev[k + 1]));
+    return OUSTER_HIP_OK;
+}
+
+int ouster_hip_voxel_downsample(ouster_hip_ctx* ctx, const ouster_hip_voxel_desc* desc, uint64_t* n_out) {
+    const int rc = voxel_validate_call(desc, n_out);
+    if (rc != OUSTER_HIP_OK) return rc == 1 ? OUSTER_HIP_OK : rc;
+    if (voxel_form(desc) == VOXEL_FORM_HOST)
+        return fail(OUSTER_HIP_ERR_UNSUPPORTED, "voxel_downsample: FIRST_N_POINT / RANDOM with max_points_per_voxel > 1 run on the host (the _host form)");
+    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    return voxel_device(ctx, desc, n_out);
+}
+
+int ouster_hip_voxel_downsample_host(ouster_hip_ctx* ctx, const ouster_hip_voxel_desc* desc, uint64_t* n_out) {
+    int rc = voxel_validate_call(desc, n_out);
+    if (rc != OUSTER_HIP_OK) return rc == 1 ? OUSTER_HIP_OK : rc;
+    if (voxel_form(desc) == VOXEL_FORM_HOST) return ouster_hip_voxel_downsample_ref(desc, n_out);
+    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (desc->n > VOXEL_MAX_POINTS) return fail(OUSTER_HIP_ERR_UNSUPPORTED, "voxel_downsample: more than 2^30 points");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t es = desc->dtype == OUSTER_HIP_F32 ? 4 : 8, stride = desc->row_stride ? desc->row_stride : desc->cols;
+    const bool wn = desc->normals != nullptr;
+    std::vector<const void*> in = {desc->points};
+    std::vector<size_t> in_bytes = {((size_t)(desc->n - 1) * stride + desc->cols) * es};
+    if (wn) in.push_back(desc->normals), in_bytes.push_back((size_t)desc->n * 24);
+    // a result of no rows still needs somewhere to point
+    static double none[3];
+    std::vector<void*> out = {desc->out_capacity ? (void*)desc->out : (void*)none};
+    std::vector<size_t> out_bytes = {(size_t)desc->out_capacity * desc->cols * 8};
+    if (wn) out.push_back(desc->out_capacity ? (void*)desc->out_normals : (void*)none), out_bytes.push_back((size_t)desc->out_capacity * 24);
+    HostPlanes hin, hout;
+    rc = hin.stage(ctx, in.data(), in_bytes.data(), (uint32_t)in.size(), 0, true);
+    // foreign output memory gets scratch that is copied back only after success: a call that refuses leaves the caller's array alone
+    if (rc == OUSTER_HIP_OK) rc = hout.stage(ctx, out.data(), out_bytes.data(), (uint32_t)out.size(), 1, false);
+    if (rc != OUSTER_HIP_OK) return rc;
+    ouster_hip_voxel_desc d = *desc;
+    d.points = hin.dev[0];
+    if (wn) d.normals = (const double*)hin.dev[1];
+    d.out = (double*)hout.dev[0];
+    if (wn) d.out_normals = (double*)hout.dev[1];
+    rc = voxel_device(ctx, &d, n_out);
+    if (rc != OUSTER_HIP_OK) return rc;
+    // only the rows of the result travel back
+    hout.bytes[0] = (size_t)*n_out * desc->cols * 8;
+    if (wn) hout.bytes[1] = (size_t)*n_out * 24;
     return hout.finish(ctx, out.data());
 }
 

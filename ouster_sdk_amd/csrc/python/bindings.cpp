@@ -16,9 +16,11 @@
 #include <pybind11/functional.h>
 
 #include "ouster/algorithm/normals.h"
+#include "ouster/algorithm/voxel_downsample.h"
 #include "ouster/core/frame_ops.h"
 #include "ouster/core/image_processing.h"
 #include "ouster/core/lidar_scan.h"
+#include "ouster/core/voxel_hash_map.h"
 #include "ouster/hip/frame_stream.h"
 #include "ouster/osf/osf.h"
 #include "ouster/pcap/indexed_pcap_reader.h"
@@ -866,6 +868,59 @@ PYBIND11_MODULE(core, m) {
             py::arg("xyz"), py::arg("range"), py::arg("xyz2"), py::arg("range2"), py::arg("sensor_origins_xyz"),
             py::arg("pixel_search_range") = 1, py::arg("min_angle_of_incidence_rad") = oa::DEFAULT_MIN_ANGLE_INCIDENCE_RAD,
             py::arg("target_distance_m") = oa::DEFAULT_TARGET_DISTANCE_METER);
+    }
+
+    // voxel down-sampling: the names, argument names and defaults of the reference's binding (python/src/cpp/client/processing.cpp);
+    // the reference's messages as ValueError.  voxel_downsample_with_normals has no Python name in the reference.
+    {
+        namespace oc = ouster::sdk::core;
+        using darr = py::array_t<double, py::array::c_style | py::array::forcecast>;
+        py::enum_<oc::VoxelDownsampleStrategy>(m, "VoxelDownsampleStrategy")
+            .value("FIRST_N_POINT", oc::VoxelDownsampleStrategy::FIRST_N_POINT)
+            .value("AVERAGE_POINT", oc::VoxelDownsampleStrategy::AVERAGE_POINT)
+            .value("RANDOM", oc::VoxelDownsampleStrategy::RANDOM);
+        auto run = [](const darr& frame, double voxel_size, size_t max_points, size_t min_pts, oc::VoxelDownsampleStrategy strategy,
+                      bool three_d) {
+            if (frame.ndim() != 2 || (three_d ? frame.shape(1) != 3 : frame.shape(1) < 3))
+                throw std::invalid_argument(three_d ? "voxel_downsample_3d: frame must be Nx3"
+                                                    : "voxel_downsample_xd: frame must be Nx>=3 (x,y,z + optional attributes)");
+            const size_t rows = static_cast<size_t>(frame.shape(0)), cols = static_cast<size_t>(frame.shape(1));
+            std::vector<double> full(rows * cols);
+            const size_t n = oc::impl::voxel_downsample_arrays(frame.data(), rows, cols, voxel_size, max_points, min_pts, strategy,
+                                                               three_d, full.data());
+            py::array_t<double> out({static_cast<py::ssize_t>(n), static_cast<py::ssize_t>(cols)});
+            if (n) std::memcpy(out.mutable_data(), full.data(), n * cols * sizeof(double));
+            return out;
+        };
+        m.def(
+            "voxel_downsample_3d",
+            [run](const darr& frame, double voxel_size, size_t max_points, size_t min_pts, oc::VoxelDownsampleStrategy strategy) {
+                return run(frame, voxel_size, max_points, min_pts, strategy, true);
+            },
+            py::arg("frame"), py::arg("voxel_size"), py::arg("max_points_per_voxel") = size_t{1}, py::arg("min_pts_threshold") = size_t{1},
+            py::arg("strategy") = oc::VoxelDownsampleStrategy::RANDOM);
+        m.def(
+            "voxel_downsample_xd",
+            [run](const darr& frame, double voxel_size, size_t max_points, size_t min_pts, oc::VoxelDownsampleStrategy strategy) {
+                return run(frame, voxel_size, max_points, min_pts, strategy, false);
+            },
+            py::arg("frame"), py::arg("voxel_size"), py::arg("max_points_per_voxel") = size_t{1}, py::arg("min_pts_threshold") = size_t{1},
+            py::arg("strategy") = oc::VoxelDownsampleStrategy::RANDOM);
+        m.def(
+            "voxel_downsample_with_normals",
+            [](const darr& points, const darr& normals, double voxel_size) {
+                if (points.ndim() != 2 || normals.ndim() != 2)
+                    throw std::invalid_argument("voxel_downsample_with_normals expects Nx3 inputs");
+                const size_t rows = static_cast<size_t>(points.shape(0));
+                std::vector<double> p(rows * 3), nr(rows * 3);
+                const size_t n = ouster::sdk::algorithm::impl::voxel_downsample_with_normals_arrays(
+                    points.data(), rows, static_cast<size_t>(points.shape(1)), normals.data(), static_cast<size_t>(normals.shape(0)),
+                    static_cast<size_t>(normals.shape(1)), voxel_size, p.data(), nr.data());
+                py::array_t<double> out_p({static_cast<py::ssize_t>(n), py::ssize_t(3)}), out_n({static_cast<py::ssize_t>(n), py::ssize_t(3)});
+                if (n) std::memcpy(out_p.mutable_data(), p.data(), n * 24), std::memcpy(out_n.mutable_data(), nr.data(), n * 24);
+                return py::make_tuple(out_p, out_n);
+            },
+            py::arg("points"), py::arg("normals"), py::arg("voxel_size"));
     }
 
     // extension over the reference's Python surface: the C++ dewarp(LidarFrame, XYZLut, min_range,
