@@ -6,17 +6,17 @@ HIPCC ?= hipcc
 CXX ?= g++
 LIB := ouster_sdk_amd/lib
 CSRC := ouster_sdk_amd/csrc
-# host/pose_util.cpp, host/normals_util.cpp and host/voxel_util.cpp are the plain C++ halves of interp_pose, normals and voxel
-# down-sampling inside libouster_hip.so (objects of their own, below)
-HOST_SRC := $(filter-out $(CSRC)/host/pose_util.cpp $(CSRC)/host/normals_util.cpp $(CSRC)/host/voxel_util.cpp,$(wildcard $(CSRC)/host/*.cpp))
+# host/pose_util.cpp, host/normals_util.cpp, host/voxel_util.cpp and host/icp_util.cpp are the plain C++ halves of interp_pose,
+# normals, voxel down-sampling and ICP inside libouster_hip.so (objects of their own, below)
+HOST_SRC := $(filter-out $(CSRC)/host/pose_util.cpp $(CSRC)/host/normals_util.cpp $(CSRC)/host/voxel_util.cpp $(CSRC)/host/icp_util.cpp,$(wildcard $(CSRC)/host/*.cpp))
 # EXPERIMENTS=1 also compiles the measured-slower kernel forms kept for A/B work (k_decode_wide_resolved, k_dwf_single, k_dwf_fused)
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++20 -fPIC -Wno-unused-result $(if $(EXPERIMENTS),-DOUSTER_EXPERIMENTS,)
 # the fused decode kernels are compiled once per packet-profile specialisation (parallel with -j)
 OBJ := $(CSRC)/_build
 SPEC_IDS := 0 1 2 3 4 5
 STREAM_IDS := 1 2 3 4 5
-HIP_OBJS := $(foreach i,$(SPEC_IDS),$(OBJ)/k_decode_$(i).o) $(foreach i,$(STREAM_IDS),$(OBJ)/k_decode_stream_$(i).o) $(OBJ)/k_standalone.o $(OBJ)/k_image.o $(OBJ)/k_frame_ops.o $(OBJ)/k_pose.o $(OBJ)/pose_util.o $(OBJ)/k_normals.o $(OBJ)/normals_util.o $(OBJ)/k_voxel.o $(OBJ)/voxel_util.o $(OBJ)/decode_launch.o $(OBJ)/decode_plan.o $(OBJ)/standalone_plan.o $(OBJ)/ouster_hip_capi.o $(OBJ)/host_pool.o
-HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/standalone_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/wide_tile.h $(CSRC)/k_image.h $(CSRC)/k_frame_ops.h $(CSRC)/k_pose.h $(CSRC)/pose_host.h $(CSRC)/k_normals.h $(CSRC)/normals_host.h $(CSRC)/k_voxel.h $(CSRC)/voxel_host.h include/ouster_hip.h
+HIP_OBJS := $(foreach i,$(SPEC_IDS),$(OBJ)/k_decode_$(i).o) $(foreach i,$(STREAM_IDS),$(OBJ)/k_decode_stream_$(i).o) $(OBJ)/k_standalone.o $(OBJ)/k_image.o $(OBJ)/k_frame_ops.o $(OBJ)/k_pose.o $(OBJ)/pose_util.o $(OBJ)/k_normals.o $(OBJ)/normals_util.o $(OBJ)/k_voxel.o $(OBJ)/voxel_util.o $(OBJ)/k_icp.o $(OBJ)/icp_util.o $(OBJ)/decode_launch.o $(OBJ)/decode_plan.o $(OBJ)/standalone_plan.o $(OBJ)/ouster_hip_capi.o $(OBJ)/host_pool.o
+HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/standalone_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/wide_tile.h $(CSRC)/k_image.h $(CSRC)/k_frame_ops.h $(CSRC)/k_pose.h $(CSRC)/pose_host.h $(CSRC)/k_normals.h $(CSRC)/normals_host.h $(CSRC)/k_voxel.h $(CSRC)/voxel_host.h $(CSRC)/voxel_dev.h $(CSRC)/k_icp.h $(CSRC)/icp_host.h include/ouster_hip.h
 ROCM ?= /opt/rocm
 CXXFLAGS := -O2 -std=c++17 -fPIC -pthread -Wall -Wextra -Iinclude -I$(CSRC)/host -I$(ROCM)/include -D__HIP_PLATFORM_AMD__
 
@@ -76,6 +76,16 @@ $(OBJ)/k_voxel.o: $(CSRC)/k_voxel.hip $(HIP_HDRS)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
 $(OBJ)/voxel_util.o: $(CSRC)/host/voxel_util.cpp $(CSRC)/voxel_host.h include/ouster_hip.h
+	@mkdir -p $(OBJ)
+	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -c -o $@ $<
+
+# ICP's correspondences, residuals and median equal a model of single IEEE operations (tests/icp_model.py), and the terms of its sums
+# are that model's: no contraction in the kernels, none in the host half (the solves, ouster_hip_icp_align_ref)
+$(OBJ)/k_icp.o: $(CSRC)/k_icp.hip $(HIP_HDRS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
+
+$(OBJ)/icp_util.o: $(CSRC)/host/icp_util.cpp $(CSRC)/icp_host.h $(CSRC)/pose_host.h include/ouster_hip.h
 	@mkdir -p $(OBJ)
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -c -o $@ $<
 

@@ -93,6 +93,22 @@ struct NormalsOptions {
     bool staggered_output = false;   ///< normal i belongs to point i of xyz_device(); false: the reference's destaggered layout
 };
 
+/** Parameters of DeviceFrameBatch::align_voxels: those of algorithm::point_to_point_align / point_to_plane_align
+ *  (algorithm/align_clouds.h) with the reference's defaults. */
+struct AlignOptions {
+    double max_corr_dist = 0.25;
+    double max_normal_angle_deg = 20.0;   ///< read on the point-to-plane route only
+};
+
+/** What DeviceFrameBatch::align_voxels returns. */
+struct AlignResult {
+    core::mat4d pose = core::mat4d::Identity();   ///< moves the batch's voxel rows onto the target; the guess where !solved
+    uint32_t iterations = 0;                      ///< passes that were run
+    uint64_t correspondences = 0;                 ///< of the last pass
+    bool solved = false;                          ///< some pass had at least 20 correspondences
+    bool point_to_plane = false;                  ///< the route taken
+};
+
 /** Parameters of DeviceFrameBatch::voxel_downsample: those of core::voxel_downsample_3d (core/voxel_hash_map.h), except that the
  *  default strategy is AVERAGE_POINT. */
 struct VoxelOptions {
@@ -263,6 +279,19 @@ class DeviceFrameBatch {
     /** Copy the rows to the host (voxel_count() x 3 doubles each; null pointers are skipped; synchronous).
      *  @throw std::invalid_argument before the first call, or for normals when the last call made none */
     void download_voxels(double* points, double* normals);
+
+    /** ICP (algorithm/align_clouds.h; csrc/k_icp.hip) of the rows of the last voxel_downsample*() -- the source -- against a target
+     *  cloud in HBM: the scan-to-scan or scan-to-map step on resident data.  Point to plane when voxel_normals_device() is not null
+     *  and target normals are given, point to point otherwise.  The result equals ouster_hip_icp_align on the same arrays bit for
+     *  bit.  Synchronous, on the batch's context.
+     *  @param target_points_device double [n_target][3]
+     *  @param target_normals_device double [n_target][3] or nullptr
+     *  @param initial_guess16 row-major 4x4, or nullptr for the identity
+     *  @throw std::runtime_error before the first voxel_downsample*(), and for HIP failures
+     *  @throw std::invalid_argument with the reference's messages for the parameters and "point_to_point_align: target point
+     *         outside the int32 cell grid" (point_to_plane_align: on that route) */
+    AlignResult align_voxels(const double* target_points_device, const double* target_normals_device, uint64_t n_target,
+                             const double* initial_guess16, const AlignOptions& options = AlignOptions());
 
     /** Per-column body_to_world poses of one frame (w x 16 doubles, row-major 4x4 each; identity
      *  until set), the input of dewarp(). */

@@ -746,6 +746,78 @@ int ouster_hip_voxel_timing(ouster_hip_ctx* ctx, int on);
 /* ms[OUSTER_HIP_VOXEL_PHASES] of the last timed call that reached the GPU; INVALID_ARGUMENT when there was none. */
 int ouster_hip_voxel_phase_ms(ouster_hip_ctx* ctx, float* ms);
 
+/* ---- ICP: point_to_point_align / point_to_plane_align ---------------------------------------- */
+/* Replaces ouster::sdk::algorithm::point_to_point_align / point_to_plane_align (ouster_algorithm/src/align_clouds.cpp:1590-1874):
+ * up to 10 passes of nearest-neighbour correspondences in a hash grid of cell max_corr_dist over the target, a Huber weight from
+ * the median residual, and a Kabsch (point) or 6x6 Gauss-Newton (plane) step.  tests/icp_model.py restates it in float64; the
+ * correspondences, residuals, count and median of a pass equal that model bit for bit.  The sums of a pass are reduced in a tree
+ * of fixed shape (a workgroup per run of ouster_hip_icp_chunk_rows() rows: in the thread, across the wave, across waves, then the
+ * partials folded in index order): a function of the inputs alone, not the reference's left fold.  No floating-point atomic.
+ * On the GPU (k_icp.hip): the target grid once per call (cell table of k_voxel.hip, scan and stable radix sort of rocPRIM, the
+ * participating rows gathered in cell order), then per pass k_icp_correspond, a radix sort of the |r| keys for the median, the sum
+ * kernels, one read-back, and the solve on the host (host/icp_util.cpp).  Intermediates live in a grow-only workspace of the context.
+ * Refused with OUSTER_HIP_ERR_INVALID_ARGUMENT before anything touches the GPU, in the reference's order: "max_corr_dist must be
+ * finite and greater than zero"; with normals "max_normal_angle_deg must be finite and in [0, 180]", "source_points and
+ * source_normals must have the same number of rows", "target_points and target_normals must have the same number of rows".
+ * Normals on one side only: "normals must be given for both clouds or for neither".  Refused by the kernels (same code, the outputs
+ * untouched): a participating target coordinate whose cell no int32 holds, "point_to_point_align: target point outside the int32
+ * cell grid" ("point_to_plane_align: ..." with normals).  A query whose cell lies outside that grid has no neighbour.
+ * Fewer than 20 rows on either side: pose = initial_guess, solved = 0, nothing is launched.  More than 2^30 rows: UNSUPPORTED. */
+#define OUSTER_HIP_ICP_SUMS 27   /* point: sum w, w x[3], w q[3], then the 9 of sum w (x - cx)(q - cq)^T row-major (16 used);
+                                    plane: the 21 entries a <= b of sum w j j^T row-major, then the 6 of sum -w j r, j = (x cross n, n) */
+typedef struct ouster_hip_icp_desc {
+    const void* source_points;     /* [n_source][source_stride] of dtype */
+    const void* target_points;     /* [n_target][target_stride] of dtype */
+    const void* source_normals;    /* [n_source_normals][source_normal_stride] of dtype, or NULL; both NULL: point to point */
+    const void* target_normals;    /* [n_target_normals][target_normal_stride] of dtype, or NULL */
+    uint64_t n_source, n_target;
+    uint64_t n_source_normals, n_target_normals;   /* rows of the normals: must equal n_source / n_target */
+    uint64_t source_stride, target_stride, source_normal_stride, target_normal_stride;   /* elements per row; 0: 3 */
+    int32_t dtype;                 /* of all four arrays: OUSTER_HIP_F32 (widened on load, exact) / OUSTER_HIP_F64 */
+    int32_t reserved;
+    double initial_guess[16];      /* row-major 4x4 */
+    double max_corr_dist;
+    double max_normal_angle_deg;   /* read with normals only */
+    /* results */
+    double pose[16];               /* row-major 4x4; initial_guess where solved == 0 */
+    uint32_t iterations;           /* passes of the loop that were run, the one that ended it included */
+    uint32_t solved;               /* 1: some pass had at least 20 correspondences */
+    uint64_t correspondences;      /* of the last pass */
+} ouster_hip_icp_desc;
+/* One pass from a given pose, with everything the tests compare. */
+typedef struct ouster_hip_icp_step_out {
+    int32_t* nn;                   /* [n_source] the neighbour's target row, -1 for none or gated out; NULL: not wanted.  Device
+                                      memory for ouster_hip_icp_step, host memory for ouster_hip_icp_step_ref */
+    double* r;                     /* [n_source] the residual, 0.0 where nn < 0; NULL: not wanted */
+    uint64_t count;                /* correspondences */
+    double median;                 /* of |r|; 0 below 20 correspondences, like everything that follows */
+    double huber_delta;
+    double sums[OUSTER_HIP_ICP_SUMS];
+    double centroid_x[3], centroid_q[3];   /* point to point: what the second pass subtracted */
+    double next_pose[16];          /* the pose after this pass (the given pose where nothing was solved) */
+    int32_t stop;                  /* 1: the loop ends after this pass */
+    int32_t solved;                /* 1: the pass had at least 20 correspondences */
+} ouster_hip_icp_step_out;
+/* Every array in device memory.  Synchronous.  Results in desc->pose / iterations / solved / correspondences. */
+int ouster_hip_icp_align(ouster_hip_ctx* ctx, ouster_hip_icp_desc* desc);
+/* The same with every array in host memory (pool memory in place, anything else through the context's grow-only scratch). */
+int ouster_hip_icp_align_host(ouster_hip_ctx* ctx, ouster_hip_icp_desc* desc);
+/* The whole algorithm on host arrays on one core, sums as left folds in source order like the reference: no GPU, no context. */
+int ouster_hip_icp_align_ref(ouster_hip_icp_desc* desc);
+/* One pass from pose16 (row-major) on device clouds; desc's results are not written.  Fewer than 20 rows on either side:
+ * INVALID_ARGUMENT. */
+int ouster_hip_icp_step(ouster_hip_ctx* ctx, const ouster_hip_icp_desc* desc, const double* pose16, ouster_hip_icp_step_out* out);
+/* The same pass on host arrays with left-fold sums. */
+int ouster_hip_icp_step_ref(const ouster_hip_icp_desc* desc, const double* pose16, ouster_hip_icp_step_out* out);
+/* Rows a workgroup of the sum kernels owns: the partial sums of a pass are those of consecutive runs of this length. */
+uint32_t ouster_hip_icp_chunk_rows(void);
+/* Times of the phases of a call, for measurement (tools/ab/icp_bench.py), like ouster_hip_voxel_timing. */
+#define OUSTER_HIP_ICP_PHASES 4   /* target grid (once); then summed over the passes: correspond, median (count + key sort +
+                                     select), sums (both point passes / the plane pass, and their folds) */
+int ouster_hip_icp_timing(ouster_hip_ctx* ctx, int on);
+/* ms[OUSTER_HIP_ICP_PHASES] of the last timed call that reached the GPU; INVALID_ARGUMENT when there was none. */
+int ouster_hip_icp_phase_ms(ouster_hip_ctx* ctx, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

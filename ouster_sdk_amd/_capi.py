@@ -114,6 +114,26 @@ class VoxelDesc(C.Structure):   # ouster_hip_voxel_desc
                 ("cols", C.c_uint32), ("dtype", C.c_int32), ("strategy", C.c_int32), ("table_log2", C.c_uint32)]
 
 
+ICP_PHASES = ("grid", "correspond", "median", "sums")   # OUSTER_HIP_ICP_PHASES
+ICP_SUMS = 27                                           # OUSTER_HIP_ICP_SUMS
+
+
+class IcpDesc(C.Structure):   # ouster_hip_icp_desc
+    _fields_ = [("source_points", C.c_void_p), ("target_points", C.c_void_p), ("source_normals", C.c_void_p),
+                ("target_normals", C.c_void_p), ("n_source", C.c_uint64), ("n_target", C.c_uint64),
+                ("n_source_normals", C.c_uint64), ("n_target_normals", C.c_uint64), ("source_stride", C.c_uint64),
+                ("target_stride", C.c_uint64), ("source_normal_stride", C.c_uint64), ("target_normal_stride", C.c_uint64),
+                ("dtype", C.c_int32), ("reserved", C.c_int32), ("initial_guess", C.c_double * 16), ("max_corr_dist", C.c_double),
+                ("max_normal_angle_deg", C.c_double), ("pose", C.c_double * 16), ("iterations", C.c_uint32), ("solved", C.c_uint32),
+                ("correspondences", C.c_uint64)]
+
+
+class IcpStepOut(C.Structure):   # ouster_hip_icp_step_out
+    _fields_ = [("nn", C.c_void_p), ("r", C.c_void_p), ("count", C.c_uint64), ("median", C.c_double), ("huber_delta", C.c_double),
+                ("sums", C.c_double * ICP_SUMS), ("centroid_x", C.c_double * 3), ("centroid_q", C.c_double * 3),
+                ("next_pose", C.c_double * 16), ("stop", C.c_int32), ("solved", C.c_int32)]
+
+
 class NormalsConsts(C.Structure):   # ouster_hip_normals_consts
     _fields_ = [("px_res_h", C.c_double), ("px_res_v", C.c_double), ("tan_safe", C.c_double), ("target_sq", C.c_double),
                 ("subtent", C.c_double)]
@@ -165,6 +185,9 @@ ABI_SYMBOLS = [
     # voxel down-sampling
     "ouster_hip_voxel_downsample", "ouster_hip_voxel_downsample_host", "ouster_hip_voxel_downsample_ref",
     "ouster_hip_voxel_timing", "ouster_hip_voxel_phase_ms",
+    # ICP
+    "ouster_hip_icp_align", "ouster_hip_icp_align_host", "ouster_hip_icp_align_ref", "ouster_hip_icp_step", "ouster_hip_icp_step_ref",
+    "ouster_hip_icp_chunk_rows", "ouster_hip_icp_timing", "ouster_hip_icp_phase_ms",
 ]
 
 _hip = None
@@ -302,6 +325,17 @@ def load_hip(private_path: Optional[str] = None):
         L.ouster_hip_voxel_downsample_ref.argtypes = [C.POINTER(VoxelDesc), C.POINTER(C.c_uint64)]
         L.ouster_hip_voxel_timing.argtypes = [vp, C.c_int]
         L.ouster_hip_voxel_phase_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    if hasattr(L, "ouster_hip_icp_align"):
+        dp = C.POINTER(C.c_double)
+        L.ouster_hip_icp_align.argtypes = [vp, C.POINTER(IcpDesc)]
+        L.ouster_hip_icp_align_host.argtypes = [vp, C.POINTER(IcpDesc)]
+        L.ouster_hip_icp_align_ref.argtypes = [C.POINTER(IcpDesc)]
+        L.ouster_hip_icp_step.argtypes = [vp, C.POINTER(IcpDesc), dp, C.POINTER(IcpStepOut)]
+        L.ouster_hip_icp_step_ref.argtypes = [C.POINTER(IcpDesc), dp, C.POINTER(IcpStepOut)]
+        L.ouster_hip_icp_chunk_rows.argtypes = []
+        L.ouster_hip_icp_chunk_rows.restype = C.c_uint32
+        L.ouster_hip_icp_timing.argtypes = [vp, C.c_int]
+        L.ouster_hip_icp_phase_ms.argtypes = [vp, C.POINTER(C.c_float)]
     if private_path is None:
         _hip = L
     return L

@@ -1,3 +1,4 @@
-"""`ouster.sdk.algorithm`: of the reference's algorithm package, the one function whose inputs this repo produces -- `normals`
-(ouster_algorithm/src/normals.cpp), on the GPU (csrc/k_normals.hip).  Same call shapes and messages as the reference's binding."""
-from ouster_sdk_amd.core import normals  # noqa: F401
+"""`ouster.sdk.algorithm`: of the reference's algorithm package, the functions whose inputs this repo produces -- `normals`
+(ouster_algorithm/src/normals.cpp) on the GPU (csrc/k_normals.hip), and `point_to_point_align` / `point_to_plane_align`
+(ouster_algorithm/src/align_clouds.cpp) on the GPU (csrc/k_icp.hip).  Same call shapes and messages as the reference's binding."""
+from ouster_sdk_amd.core import normals, point_to_plane_align, point_to_point_align  # noqa: F401

@@ -771,6 +771,33 @@ uint64_t DeviceFrameBatch::voxel_downsample_with_normals(double voxel_size, int 
     return voxel_run_(d_xyz_[k].data(), normals_device(k), static_cast<uint64_t>(n_frames_) * h_ * w_, voxel_size, VoxelOptions());
 }
 
+AlignResult DeviceFrameBatch::align_voxels(const double* target_points_device, const double* target_normals_device, uint64_t n_target,
+                                           const double* initial_guess16, const AlignOptions& o) {
+    ScopedContext on_my_context(ctx_);
+    if (!vox_made_) throw std::runtime_error("DeviceFrameBatch::align_voxels: voxel_downsample() or voxel_downsample_with_normals() first");
+    static const double none[3] = {0, 0, 0};   // an empty cloud still needs somewhere to point; it is never read
+    AlignResult r;
+    r.point_to_plane = vox_normals_ && target_normals_device != nullptr;
+    ouster_hip_icp_desc d{};
+    d.source_points = vox_count_ ? d_vox_pts_.data() : none;
+    d.target_points = n_target ? target_points_device : none;
+    d.n_source = vox_count_, d.n_target = n_target;
+    if (r.point_to_plane) {
+        d.source_normals = vox_count_ ? d_vox_nrm_.data() : none, d.target_normals = target_normals_device;
+        d.n_source_normals = vox_count_, d.n_target_normals = n_target;
+    }
+    d.dtype = OUSTER_HIP_F64;
+    if (initial_guess16) std::memcpy(d.initial_guess, initial_guess16, sizeof d.initial_guess);
+    else std::memcpy(d.initial_guess, core::mat4d::Identity().data(), sizeof d.initial_guess);
+    d.max_corr_dist = o.max_corr_dist, d.max_normal_angle_deg = o.max_normal_angle_deg;
+    const int rc = ouster_hip_icp_align(default_ctx(), &d);
+    if (rc == OUSTER_HIP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(ouster_hip_last_error());
+    if (rc != OUSTER_HIP_OK) throw std::runtime_error(ouster_hip_last_error());
+    r.pose = core::mat4d::FromRowMajor(d.pose);
+    r.iterations = d.iterations, r.correspondences = d.correspondences, r.solved = d.solved != 0;
+    return r;
+}
+
 double* DeviceFrameBatch::voxels_device() { return vox_made_ ? static_cast<double*>(d_vox_pts_.data()) : nullptr; }
 
 double* DeviceFrameBatch::voxel_normals_device() {

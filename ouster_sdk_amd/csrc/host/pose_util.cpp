@@ -116,6 +116,45 @@ void pose_log(const double (&m)[4][4], double (&twist)[6]) {
 
 }  // namespace
 
+// PoseV::exp (transform_vector.cpp:40-50, 96-104), as tests/pose_model.py pose_exp: the ICP step of host/icp_util.cpp
+void pose_exp(const double* twist6, double* out16) {
+    const double r[3] = {twist6[0], twist6[1], twist6[2]};
+    const double angle = std::sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+    const double s = std::sin(angle), c = std::cos(angle);
+    double a[3][3], rot[3][3], vm[3][3];
+    if (angle < std::sqrt(EPS)) {
+        skew(r, a);
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) rot[i][j] = (i == j ? 1.0 : 0.0) + a[i][j];
+    } else {
+        const double ax[3] = {r[0] / angle, r[1] / angle, r[2] / angle};
+        double ka[3][3], aa[3][3];
+        skew(ax, a);
+        const double k = 1.0 - c;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) ka[i][j] = k * a[i][j];
+        matmul<3>(ka, a, aa);
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) rot[i][j] = ((i == j ? 1.0 : 0.0) + s * a[i][j]) + aa[i][j];
+    }
+    vee(r, angle, s, c, vm);
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) out16[4 * i + j] = rot[i][j];
+        out16[4 * i + 3] = (vm[i][0] * twist6[3] + vm[i][1] * twist6[4]) + vm[i][2] * twist6[5];
+    }
+    out16[12] = out16[13] = out16[14] = 0.0;
+    out16[15] = 1.0;
+}
+
+void pose_compose(const double* a16, const double* b16, double* out16) {
+    double a[4][4], b[4][4], r[4][4];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) a[i][j] = a16[4 * i + j], b[i][j] = b16[4 * i + j];
+    matmul<4>(a, b, r);
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) out16[4 * i + j] = r[i][j];
+}
+
 const char* pose_validate_known(const double* x_known, const double* poses_known, uint32_t k) {
     if (k < 2) return "Not enough evaluation poses for interpolation";
     if (!x_known || !poses_known) return "x_known and poses_known sizes are not matching";

@@ -1,0 +1,84 @@
+// k_icp.h -- launch interface of the ICP kernels (k_icp.hip): the target grid (keys, then the cell table, ids, stable sort and
+// segments of k_voxel.hip, then the slots and the gathered rows), the correspondences of a pass, the median of their residuals and
+// the sums behind the solve.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/ouster_hip.h"
+#include "icp_host.h"
+#include "k_voxel.h"
+
+namespace ouster_hip_dev {
+
+constexpr uint32_t ICP_WG = 256;
+constexpr uint32_t ICP_ROWS_PER_THREAD = 4;
+constexpr uint32_t ICP_CHUNK = ICP_WG * ICP_ROWS_PER_THREAD;   // ouster_hip_icp_chunk_rows(): rows one workgroup of the sum kernels owns
+constexpr uint64_t ICP_NO_KEY = ~0ull;                          // the sort key of a row without a correspondence: after every |r|
+constexpr uint32_t ICP_STATUS_GRID = 1;                         // a participating target row outside the int32 cell grid
+
+// a slot of the cell table as the queries read it: the cell and where its rows start in the gathered order; begin < 0: free
+struct alignas(16) IcpSlot {
+    int32_t x, y, z;
+    int32_t begin;
+};
+
+// what a pass reads back (after the VoxelHeader of the grid)
+struct IcpHeader {
+    uint32_t status;   // 0 or ICP_STATUS_GRID
+    uint32_t count;    // correspondences of the pass
+    double median, huber_delta;
+    double centroid_x[3], centroid_q[3];
+    double sums[OUSTER_HIP_ICP_SUMS];
+};
+struct IcpReadback {
+    VoxelHeader grid;   // status: the table ran full (cannot happen); n_vox: cells
+    IcpHeader pass;
+};
+
+struct IcpArgs {
+    const void *src, *tgt, *src_n, *tgt_n;   // [n][stride] of f32 / f64
+    uint64_t src_stride, tgt_stride, src_n_stride, tgt_n_stride;
+    uint32_t n_src, n_tgt;
+    int32_t f32, plane;
+    double inv;            // 1.0 / max_corr_dist
+    double max_d2;         // max_corr_dist * max_corr_dist
+    double max_corr_dist;
+    double cos_gate;
+    double pose[16];       // of the pass
+    IcpReadback* rb;
+    // target side, [n_tgt] unless noted: what the k_voxel.hip launchers fill (VoxelArgs), then
+    VoxelKey* keys;
+    int32_t* table;
+    uint32_t table_mask;
+    uint32_t *first_id, *svid, *sidx, *seg_begin, *seg_end;
+    IcpSlot* slots;        // [table_mask + 1]
+    uint32_t* slot_end;    // [table_mask + 1]
+    double* rows;          // [n_tgt][3 or 6] the participating target points (and unit normals) in cell order
+    // source side, [n_src]
+    int32_t* nn;
+    double* r;
+    uint64_t *key, *key_sorted;
+    uint32_t* flag;
+    double* xq;            // [n_src][6]: x, then q (point) or the unit target normal (plane)
+    double* partials;      // [chunks][OUSTER_HIP_ICP_SUMS]
+};
+
+inline uint32_t icp_chunks(uint32_t n_src) { return (n_src + ICP_CHUNK - 1) / ICP_CHUNK; }
+
+hipError_t launch_icp_keys(const IcpArgs& a, hipStream_t st);         // keys, pass.status
+hipError_t launch_icp_slots(const IcpArgs& a, hipStream_t st);        // slots, slot_end (after the segments)
+hipError_t launch_icp_gather(const IcpArgs& a, hipStream_t st);       // rows
+hipError_t launch_icp_correspond(const IcpArgs& a, hipStream_t st);   // nn, r, key, flag, xq
+
+// The device-wide pieces (hipcc only): the bytes of temporary storage a call needs, the grid once per call and one pass, both on the
+// stream without a synchronisation.  `va` carries the target-side arrays for the launchers of k_voxel.h (n = n_tgt).
+// ev: nullptr, or events recorded after the grid (1) / after correspond, median and sums (3).
+#ifdef __HIPCC__
+hipError_t icp_temp_bytes(uint32_t n_src, uint32_t n_tgt, size_t* bytes);
+hipError_t icp_grid_run(const IcpArgs& a, const VoxelArgs& va, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t icp_pass_run(const IcpArgs& a, void* temp, size_t temp_bytes, hipStream_t st, hipEvent_t* ev = nullptr);
+#endif
+
+}  // namespace ouster_hip_dev

@@ -24,6 +24,7 @@
 #include "k_normals.h"
 #include "k_pose.h"
 #include "k_voxel.h"
+#include "k_icp.h"
 #include "ouster_hip_dev.h"
 
 using namespace ouster_hip_dev;
@@ -110,6 +111,11 @@ struct ouster_hip_ctx {
     bool voxel_timing = false, voxel_timed = false;   // ouster_hip_voxel_timing: events around the phases of a call
     hipEvent_t voxel_ev[OUSTER_HIP_VOXEL_PHASES + 1] = {};
     DevBuf voxel_ws;                     // ouster_hip_voxel_downsample: keys, table, ids, sorted indices, gathered rows, sort temporaries
+    bool icp_timing = false;             // ouster_hip_icp_timing: events around the phases of a call; icp_timed_passes: of the last one
+    uint32_t icp_timed_passes = 0;
+    bool icp_timed = false;
+    hipEvent_t icp_ev[2 + 4 * 10] = {};  //   start, after the grid, then per pass: start, after correspond, after median, after sums
+    DevBuf icp_ws;                       // ouster_hip_icp_*: the target grid, the per-row outputs of a pass, partial sums, sort temporaries
     DevBuf user_scratch[8];              // ouster_hip_ctx_scratch: what the *_host calls and bindings stage through
     uint32_t resident_wgs = 512;         // 2 workgroups (80 KB LDS each) per CU
     uint32_t cus = 256;                  // compute units (k_decode_stream: one persistent workgroup each)
@@ -340,6 +346,9 @@ void ouster_hip_ctx_destroy(ouster_hip_ctx* c) {
     c->fops_tables.release();
     c->normals_pairs.release();
     c->voxel_ws.release();
+    c->icp_ws.release();
+    for (hipEvent_t& e : c->icp_ev)
+        if (e) (void)hipEventDestroy(e), e = nullptr;
     for (hipEvent_t& e : c->voxel_ev)
         if (e) (void)hipEventDestroy(e), e = nullptr;
     if (c->fops_ev) (void)hipEventDestroy(c->fops_ev);
@@ -2464,6 +2473,220 @@ int ouster_hip_voxel_downsample_host(ouster_hip_ctx* ctx, const ouster_hip_voxel
     hout.bytes[0] = (size_t)*n_out * desc->cols * 8;
     if (wn) hout.bytes[1] = (size_t)*n_out * 24;
     return hout.finish(ctx, out.data());
+}
+
+// ---- ICP: point_to_point_align / point_to_plane_align (k_icp.hip, host/icp_util.cpp) -------------------
+namespace {
+struct IcpCall {
+    IcpArgs a{};
+    VoxelArgs va{};
+    uint8_t* temp = nullptr;
+    size_t temp_bytes = 0;
+    IcpMethod method = ICP_POINT;
+};
+
+// what every entry point refuses before a GPU is looked at; 1: fewer than 20 rows on a side (the guess is the answer)
+int icp_validate_call(const ouster_hip_icp_desc* d) {
+    if (!d) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (const char* msg = icp_validate(d)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (d->n_source > ICP_MAX_ROWS || d->n_target > ICP_MAX_ROWS) return fail(OUSTER_HIP_ERR_UNSUPPORTED, "icp: more than 2^30 rows");
+    return d->n_source < ICP_MIN_POINTS || d->n_target < ICP_MIN_POINTS ? 1 : OUSTER_HIP_OK;
+}
+
+void icp_guess_is_the_answer(ouster_hip_icp_desc* d) {
+    memcpy(d->pose, d->initial_guess, sizeof d->pose);
+    d->iterations = 0, d->solved = 0, d->correspondences = 0;
+}
+
+// d: every array in device memory, validated, at least 20 rows a side.  Lays the workspace out; launches nothing
+int icp_prepare(ouster_hip_ctx* ctx, const ouster_hip_icp_desc* d, IcpCall& c) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    IcpArgs& a = c.a;
+    c.method = icp_method(d);
+    a.src = d->source_points, a.tgt = d->target_points, a.src_n = d->source_normals, a.tgt_n = d->target_normals;
+    a.src_stride = d->source_stride ? d->source_stride : 3, a.tgt_stride = d->target_stride ? d->target_stride : 3;
+    a.src_n_stride = d->source_normal_stride ? d->source_normal_stride : 3, a.tgt_n_stride = d->target_normal_stride ? d->target_normal_stride : 3;
+    a.n_src = (uint32_t)d->n_source, a.n_tgt = (uint32_t)d->n_target;
+    a.f32 = d->dtype == OUSTER_HIP_F32, a.plane = c.method == ICP_PLANE;
+    a.inv = 1.0 / d->max_corr_dist;
+    a.max_d2 = d->max_corr_dist * d->max_corr_dist;
+    a.max_corr_dist = d->max_corr_dist;
+    a.cos_gate = a.plane ? icp_cos_gate(d->max_normal_angle_deg) : 0.0;
+    uint32_t log2 = 1;
+    while ((1ull << log2) < 2 * d->n_target) ++log2;
+    a.table_mask = (uint32_t)((1ull << log2) - 1);
+    HIP_TRY(icp_temp_bytes(a.n_src, a.n_tgt, &c.temp_bytes));
+    const size_t nt = a.n_tgt, ns = a.n_src, slots = (size_t)a.table_mask + 1;
+    size_t total = 0;
+    auto take = [&total](size_t bytes) {
+        const size_t at = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t o_rb = take(sizeof(IcpReadback)), o_keys = take(nt * sizeof(VoxelKey)), o_table = take(slots * 4), o_slot = take(nt * 4),
+                 o_first = take(nt * 4), o_first_id = take(nt * 4), o_vid = take(nt * 4), o_idx = take(nt * 4), o_svid = take(nt * 4),
+                 o_sidx = take(nt * 4), o_begin = take(nt * 4), o_end = take(nt * 4), o_slots = take(slots * sizeof(IcpSlot)),
+                 o_slot_end = take(slots * 4), o_rows = take(nt * 8 * (a.plane ? 6 : 3)), o_nn = take(ns * 4), o_r = take(ns * 8),
+                 o_key = take(ns * 8), o_key_sorted = take(ns * 8), o_flag = take(ns * 4), o_xq = take(ns * 48),
+                 o_partials = take((size_t)icp_chunks(a.n_src) * OUSTER_HIP_ICP_SUMS * 8), o_temp = take(c.temp_bytes);
+    if (ctx->icp_ws.cap < total) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (ctx->icp_ws.ensure(total)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (icp workspace, %zu bytes)", total);
+    }
+    uint8_t* ws = (uint8_t*)ctx->icp_ws.p;
+    a.rb = (IcpReadback*)(ws + o_rb), a.keys = (VoxelKey*)(ws + o_keys), a.table = (int32_t*)(ws + o_table);
+    a.first_id = (uint32_t*)(ws + o_first_id), a.svid = (uint32_t*)(ws + o_svid), a.sidx = (uint32_t*)(ws + o_sidx);
+    a.seg_begin = (uint32_t*)(ws + o_begin), a.seg_end = (uint32_t*)(ws + o_end);
+    a.slots = (IcpSlot*)(ws + o_slots), a.slot_end = (uint32_t*)(ws + o_slot_end), a.rows = (double*)(ws + o_rows);
+    a.nn = (int32_t*)(ws + o_nn), a.r = (double*)(ws + o_r), a.key = (uint64_t*)(ws + o_key), a.key_sorted = (uint64_t*)(ws + o_key_sorted);
+    a.flag = (uint32_t*)(ws + o_flag), a.xq = (double*)(ws + o_xq), a.partials = (double*)(ws + o_partials);
+    c.temp = ws + o_temp;
+    // the target side as the launchers of k_voxel.h see it
+    VoxelArgs& v = c.va;
+    v.n = a.n_tgt, v.hdr = &a.rb->grid, v.keys = a.keys, v.table = a.table, v.table_mask = a.table_mask;
+    v.slot = (uint32_t*)(ws + o_slot), v.first = (uint32_t*)(ws + o_first), v.first_id = a.first_id;
+    v.vid = (uint32_t*)(ws + o_vid), v.idx = (uint32_t*)(ws + o_idx), v.svid = a.svid, v.sidx = a.sidx;
+    v.seg_begin = a.seg_begin, v.seg_end = a.seg_end;
+    return OUSTER_HIP_OK;
+}
+
+// one pass from `pose` and its read-back; the grid's refusals come with the first one
+int icp_pass(ouster_hip_ctx* ctx, IcpCall& c, const double* pose, IcpReadback& rb, hipEvent_t* ev) {
+    memcpy(c.a.pose, pose, sizeof c.a.pose);
+    if (ev) HIP_TRY(hipEventRecord(ev[0], ctx->stream));
+    HIP_TRY(icp_pass_run(c.a, c.temp, c.temp_bytes, ctx->stream, ev ? ev + 1 : nullptr));
+    HIP_TRY(hipMemcpyAsync(&rb, c.a.rb, sizeof rb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (rb.grid.status) return fail(OUSTER_HIP_ERR_RUNTIME, "icp: hash table exhausted");
+    if (rb.pass.status) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", icp_msg_grid(c.method));
+    return OUSTER_HIP_OK;
+}
+
+// d: every array in device memory, validated, at least 20 rows a side
+int icp_device(ouster_hip_ctx* ctx, ouster_hip_icp_desc* d) {
+    IcpCall c;
+    int rc = icp_prepare(ctx, d, c);
+    if (rc != OUSTER_HIP_OK) return rc;
+    const bool timing = ctx->icp_timing;
+    ctx->icp_timed = false;
+    if (timing) HIP_TRY(hipEventRecord(ctx->icp_ev[0], ctx->stream));
+    HIP_TRY(icp_grid_run(c.a, c.va, c.temp, c.temp_bytes, ctx->stream));
+    if (timing) HIP_TRY(hipEventRecord(ctx->icp_ev[1], ctx->stream));
+    double pose[16];
+    memcpy(pose, d->initial_guess, sizeof pose);
+    uint32_t iterations = 0, solved = 0;
+    uint64_t count = 0;
+    for (uint32_t it = 0; it < ICP_MAX_ITERATIONS; ++it) {
+        IcpReadback rb{};
+        rc = icp_pass(ctx, c, pose, rb, timing ? ctx->icp_ev + 2 + 4 * it : nullptr);
+        if (rc != OUSTER_HIP_OK) return rc;
+        ++iterations;
+        count = rb.pass.count;
+        solved |= count >= ICP_MIN_POINTS;
+        double next[16];
+        bool stop = true;
+        icp_finish_pass(c.method, count, rb.pass.sums, rb.pass.centroid_x, rb.pass.centroid_q, pose, next, &stop);
+        memcpy(pose, next, sizeof pose);
+        if (stop) break;
+    }
+    memcpy(d->pose, solved ? pose : d->initial_guess, sizeof pose);
+    d->iterations = iterations, d->solved = solved, d->correspondences = count;
+    ctx->icp_timed = timing;
+    ctx->icp_timed_passes = iterations;
+    return OUSTER_HIP_OK;
+}
+}  // namespace
+
+uint32_t ouster_hip_icp_chunk_rows(void) { return ICP_CHUNK; }
+
+int ouster_hip_icp_timing(ouster_hip_ctx* ctx, int on) {
+    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (on)
+        for (hipEvent_t& e : ctx->icp_ev)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+    ctx->icp_timing = on != 0;
+    ctx->icp_timed = false;
+    return OUSTER_HIP_OK;
+}
+
+int ouster_hip_icp_phase_ms(ouster_hip_ctx* ctx, float* ms) {
+    if (!ctx || !ms) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!ctx->icp_timed) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "icp: no timed call (ouster_hip_icp_timing)");
+    for (int k = 0; k < OUSTER_HIP_ICP_PHASES; ++k) ms[k] = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms[0], ctx->icp_ev[0], ctx->icp_ev[1]));
+    for (uint32_t it = 0; it < ctx->icp_timed_passes; ++it)
+        for (int k = 0; k < 3; ++k) {
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, ctx->icp_ev[2 + 4 * it + k], ctx->icp_ev[2 + 4 * it + k + 1]));
+            ms[1 + k] += t;
+        }
+    return OUSTER_HIP_OK;
+}
+
+int ouster_hip_icp_align(ouster_hip_ctx* ctx, ouster_hip_icp_desc* desc) {
+    const int rc = icp_validate_call(desc);
+    if (rc < 0) return rc;
+    if (rc == 1) return icp_guess_is_the_answer(desc), OUSTER_HIP_OK;
+    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    return icp_device(ctx, desc);
+}
+
+int ouster_hip_icp_step(ouster_hip_ctx* ctx, const ouster_hip_icp_desc* desc, const double* pose16, ouster_hip_icp_step_out* out) {
+    if (!pose16 || !out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = icp_validate_call(desc);
+    if (rc < 0) return rc;
+    if (rc == 1) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "icp_step: fewer than 20 rows");
+    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    IcpCall c;
+    rc = icp_prepare(ctx, desc, c);
+    if (rc != OUSTER_HIP_OK) return rc;
+    HIP_TRY(icp_grid_run(c.a, c.va, c.temp, c.temp_bytes, ctx->stream));
+    IcpReadback rb{};
+    rc = icp_pass(ctx, c, pose16, rb, nullptr);
+    if (rc != OUSTER_HIP_OK) return rc;
+    if (out->nn) HIP_TRY(hipMemcpyAsync(out->nn, c.a.nn, (size_t)c.a.n_src * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    if (out->r) HIP_TRY(hipMemcpyAsync(out->r, c.a.r, (size_t)c.a.n_src * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const bool solved = rb.pass.count >= ICP_MIN_POINTS;
+    out->count = rb.pass.count;
+    out->median = rb.pass.median, out->huber_delta = rb.pass.huber_delta;
+    for (int k = 0; k < OUSTER_HIP_ICP_SUMS; ++k) out->sums[k] = solved ? rb.pass.sums[k] : 0.0;
+    for (int k = 0; k < 3; ++k) {
+        out->centroid_x[k] = solved && c.method == ICP_POINT ? rb.pass.centroid_x[k] : 0.0;
+        out->centroid_q[k] = solved && c.method == ICP_POINT ? rb.pass.centroid_q[k] : 0.0;
+    }
+    bool stop = true;
+    icp_finish_pass(c.method, rb.pass.count, rb.pass.sums, rb.pass.centroid_x, rb.pass.centroid_q, pose16, out->next_pose, &stop);
+    out->stop = stop, out->solved = solved;
+    return OUSTER_HIP_OK;
+}
+
+int ouster_hip_icp_align_host(ouster_hip_ctx* ctx, ouster_hip_icp_desc* desc) {
+    int rc = icp_validate_call(desc);
+    if (rc < 0) return rc;
+    if (rc == 1) return icp_guess_is_the_answer(desc), OUSTER_HIP_OK;
+    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t es = desc->dtype == OUSTER_HIP_F32 ? 4 : 8;
+    auto bytes = [es](uint64_t n, uint64_t stride) { return ((size_t)(n - 1) * (stride ? stride : 3) + 3) * es; };
+    std::vector<const void*> in = {desc->source_points, desc->target_points};
+    std::vector<size_t> in_bytes = {bytes(desc->n_source, desc->source_stride), bytes(desc->n_target, desc->target_stride)};
+    if (desc->source_normals) {
+        in.push_back(desc->source_normals), in_bytes.push_back(bytes(desc->n_source, desc->source_normal_stride));
+        in.push_back(desc->target_normals), in_bytes.push_back(bytes(desc->n_target, desc->target_normal_stride));
+    }
+    HostPlanes hin;
+    rc = hin.stage(ctx, in.data(), in_bytes.data(), (uint32_t)in.size(), 0, true);
+    if (rc != OUSTER_HIP_OK) return rc;
+    ouster_hip_icp_desc d = *desc;
+    d.source_points = hin.dev[0], d.target_points = hin.dev[1];
+    if (desc->source_normals) d.source_normals = hin.dev[2], d.target_normals = hin.dev[3];
+    rc = icp_device(ctx, &d);
+    if (rc != OUSTER_HIP_OK) return rc;
+    memcpy(desc->pose, d.pose, sizeof d.pose);
+    desc->iterations = d.iterations, desc->solved = d.solved, desc->correspondences = d.correspondences;
+    return OUSTER_HIP_OK;
 }
 
 // ---- timing ------------------------------------------------------------------------------------

@@ -16,6 +16,10 @@ const char* pose_validate_pair(double t0, double t1);
 const char* pose_validate_interp(const double* x_interp, size_t n, char* msg, size_t msg_size);
 // one row of the table: log(inv(a) b) / (t1 - t0) next to t0 and a (pose_util.h:216-222)
 void pose_segment(double t0, const double* a16, double t1, const double* b16, double* seg24);
+// PoseV::exp of (rotation, translation) as a row-major 4x4, and the full 4x4 product a b with every sum left to right: shared
+// with the ICP step (host/icp_util.cpp)
+void pose_exp(const double* twist6, double* out16);
+void pose_compose(const double* a16, const double* b16, double* out16);
 
 // the C ABI's error channel (ouster_hip_capi.hip): stores the thread's message, returns `code`
 int fail_msg(int code, const char* msg);

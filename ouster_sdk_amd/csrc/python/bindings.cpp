@@ -15,6 +15,7 @@
 
 #include <pybind11/functional.h>
 
+#include "ouster/algorithm/align_clouds.h"
 #include "ouster/algorithm/normals.h"
 #include "ouster/algorithm/voxel_downsample.h"
 #include "ouster/core/frame_ops.h"
@@ -921,6 +922,45 @@ PYBIND11_MODULE(core, m) {
                 return py::make_tuple(out_p, out_n);
             },
             py::arg("points"), py::arg("normals"), py::arg("voxel_size"));
+    }
+
+    // ICP: the names, keywords and defaults of ouster.sdk.algorithm.point_to_point_align / point_to_plane_align; the reference's
+    // messages as ValueError
+    {
+        using darr = py::array_t<double, py::array::c_style | py::array::forcecast>;
+        auto run = [](const darr& src, const darr& tgt, const darr* src_n, const darr* tgt_n, const py::object& guess, double max_corr_dist,
+                      double max_normal_angle_deg) {
+            auto rows_of = [](const darr& a, const char* name) {
+                if (a.ndim() != 2 || a.shape(1) != 3) throw std::invalid_argument(std::string(name) + " must be Nx3");
+                return static_cast<size_t>(a.shape(0));
+            };
+            const size_t ns = rows_of(src, "source_points"), nt = rows_of(tgt, "target_points");
+            const size_t nsn = src_n ? rows_of(*src_n, "source_normals") : 0, ntn = tgt_n ? rows_of(*tgt_n, "target_normals") : 0;
+            double g[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+            if (!guess.is_none()) {
+                const darr ga = guess.cast<darr>();
+                if (ga.size() != 16) throw std::invalid_argument("initial_guess must be 4x4");
+                std::memcpy(g, ga.data(), sizeof g);
+            }
+            static const double none[3] = {0, 0, 0};
+            py::array_t<double> out({py::ssize_t(4), py::ssize_t(4)});
+            ouster::sdk::algorithm::impl::align_arrays(src.data(), ns, tgt.data(), nt, src_n ? (nsn ? src_n->data() : none) : nullptr, nsn,
+                                                       tgt_n ? (ntn ? tgt_n->data() : none) : nullptr, ntn, g, max_corr_dist,
+                                                       max_normal_angle_deg, out.mutable_data());
+            return out;
+        };
+        m.def(
+            "point_to_point_align",
+            [run](const darr& src, const darr& tgt, const py::object& guess, double max_corr_dist) {
+                return run(src, tgt, nullptr, nullptr, guess, max_corr_dist, 20.0);
+            },
+            py::arg("source_points"), py::arg("target_points"), py::arg("initial_guess") = py::none(), py::arg("max_corr_dist") = 0.25);
+        m.def(
+            "point_to_plane_align",
+            [run](const darr& src, const darr& tgt, const darr& src_n, const darr& tgt_n, const py::object& guess, double max_corr_dist,
+                  double max_normal_angle_deg) { return run(src, tgt, &src_n, &tgt_n, guess, max_corr_dist, max_normal_angle_deg); },
+            py::arg("source_points"), py::arg("target_points"), py::arg("source_normals"), py::arg("target_normals"),
+            py::arg("initial_guess") = py::none(), py::arg("max_corr_dist") = 0.25, py::arg("max_normal_angle_deg") = 20.0);
     }
 
     // extension over the reference's Python surface: the C++ dewarp(LidarFrame, XYZLut, min_range,
