@@ -15,8 +15,9 @@ HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++20 -fPIC -Wno-unused-result $(if $
 OBJ := $(CSRC)/_build
 SPEC_IDS := 0 1 2 3 4 5
 STREAM_IDS := 1 2 3 4 5
-HIP_OBJS := $(foreach i,$(SPEC_IDS),$(OBJ)/k_decode_$(i).o) $(foreach i,$(STREAM_IDS),$(OBJ)/k_decode_stream_$(i).o) $(OBJ)/k_standalone.o $(OBJ)/k_image.o $(OBJ)/k_frame_ops.o $(OBJ)/k_pose.o $(OBJ)/pose_util.o $(OBJ)/k_normals.o $(OBJ)/normals_util.o $(OBJ)/k_voxel.o $(OBJ)/voxel_util.o $(OBJ)/k_icp.o $(OBJ)/icp_util.o $(OBJ)/decode_launch.o $(OBJ)/decode_plan.o $(OBJ)/standalone_plan.o $(OBJ)/ouster_hip_capi.o $(OBJ)/host_pool.o
-HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/standalone_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/wide_tile.h $(CSRC)/k_image.h $(CSRC)/k_frame_ops.h $(CSRC)/k_pose.h $(CSRC)/pose_host.h $(CSRC)/k_normals.h $(CSRC)/normals_host.h $(CSRC)/k_voxel.h $(CSRC)/voxel_host.h $(CSRC)/voxel_dev.h $(CSRC)/k_icp.h $(CSRC)/icp_host.h include/ouster_hip.h
+FEATURES := image frame_ops pose normals voxel icp
+HIP_OBJS := $(foreach i,$(SPEC_IDS),$(OBJ)/k_decode_$(i).o) $(foreach i,$(STREAM_IDS),$(OBJ)/k_decode_stream_$(i).o) $(OBJ)/k_standalone.o $(OBJ)/k_image.o $(OBJ)/k_frame_ops.o $(OBJ)/k_pose.o $(OBJ)/pose_util.o $(OBJ)/k_normals.o $(OBJ)/normals_util.o $(OBJ)/k_voxel.o $(OBJ)/voxel_util.o $(OBJ)/k_icp.o $(OBJ)/icp_util.o $(OBJ)/decode_launch.o $(OBJ)/decode_plan.o $(OBJ)/standalone_plan.o $(OBJ)/ouster_hip_capi.o $(FEATURES:%=$(OBJ)/capi_%.o) $(OBJ)/host_pool.o
+HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/standalone_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/wide_tile.h $(CSRC)/k_image.h $(CSRC)/k_frame_ops.h $(CSRC)/k_pose.h $(CSRC)/pose_host.h $(CSRC)/k_normals.h $(CSRC)/normals_host.h $(CSRC)/k_voxel.h $(CSRC)/voxel_host.h $(CSRC)/voxel_dev.h $(CSRC)/k_icp.h $(CSRC)/icp_host.h $(CSRC)/capi_internal.h $(CSRC)/carve.h include/ouster_hip.h
 ROCM ?= /opt/rocm
 CXXFLAGS := -O2 -std=c++17 -fPIC -pthread -Wall -Wextra -Iinclude -I$(CSRC)/host -I$(ROCM)/include -D__HIP_PLATFORM_AMD__
 
@@ -35,59 +36,24 @@ $(OBJ)/k_decode_%.o: $(CSRC)/k_decode.hip $(HIP_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -DOUSTER_SPEC_ID=$* -c -o $@ $<
 
-# the display-image kernels round every step on its own, like the reference's host build: no FMA contraction
-$(OBJ)/k_image.o: $(CSRC)/k_image.hip $(HIP_HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
+# no FMA contraction in kernels held to models that round every step on its own, none in their plain C++ halves (host/*_util.cpp):
+#   k_image      the display images round like the reference's host build
+#   k_frame_ops  compares converted values only; kept so that no later arithmetic can feed a comparison fused
+#   k_pose       interp_pose / transform equal tests/pose_model.py
+#   k_normals    normals equals tests/normals_model.py
+#   k_voxel      the sums are left folds of single IEEE operations (tests/voxel_model.py)
+#   k_icp        correspondences, residuals, median and the terms of the sums equal tests/icp_model.py
+NO_CONTRACT := k_image k_frame_ops k_pose k_normals k_voxel k_icp
+$(NO_CONTRACT:%=$(OBJ)/%.o): HIPFLAGS += -ffp-contract=off
 
 $(OBJ)/%.o: $(CSRC)/%.hip $(HIP_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-# frame_ops compares converted values only; kept off contraction all the same, so that no later arithmetic can feed a comparison fused
-$(OBJ)/k_frame_ops.o: $(CSRC)/k_frame_ops.hip $(HIP_HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
-
-# interp_pose / transform are held to a model that rounds every step on its own (tests/pose_model.py): no contraction in the
-# kernel, none in the host half that builds the per-segment table
-$(OBJ)/k_pose.o: $(CSRC)/k_pose.hip $(HIP_HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
-
-$(OBJ)/pose_util.o: $(CSRC)/host/pose_util.cpp $(CSRC)/pose_host.h include/ouster_hip.h
+$(OBJ)/%_util.o: $(CSRC)/host/%_util.cpp $(CSRC)/%_host.h include/ouster_hip.h
 	@mkdir -p $(OBJ)
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -c -o $@ $<
-
-# normals equals a model that rounds every step on its own (tests/normals_model.py): no contraction in the kernels, none in the
-# host half that makes the per-call constants with libm
-$(OBJ)/k_normals.o: $(CSRC)/k_normals.hip $(HIP_HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
-
-$(OBJ)/normals_util.o: $(CSRC)/host/normals_util.cpp $(CSRC)/normals_host.h include/ouster_hip.h
-	@mkdir -p $(OBJ)
-	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -c -o $@ $<
-
-# voxel down-sampling equals a model whose sums are left folds of single IEEE operations (tests/voxel_model.py): no contraction in
-# the kernels, none in the host restatement (ouster_hip_voxel_downsample_ref)
-$(OBJ)/k_voxel.o: $(CSRC)/k_voxel.hip $(HIP_HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
-
-$(OBJ)/voxel_util.o: $(CSRC)/host/voxel_util.cpp $(CSRC)/voxel_host.h include/ouster_hip.h
-	@mkdir -p $(OBJ)
-	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -c -o $@ $<
-
-# ICP's correspondences, residuals and median equal a model of single IEEE operations (tests/icp_model.py), and the terms of its sums
-# are that model's: no contraction in the kernels, none in the host half (the solves, ouster_hip_icp_align_ref)
-$(OBJ)/k_icp.o: $(CSRC)/k_icp.hip $(HIP_HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
-
-$(OBJ)/icp_util.o: $(CSRC)/host/icp_util.cpp $(CSRC)/icp_host.h $(CSRC)/pose_host.h include/ouster_hip.h
-	@mkdir -p $(OBJ)
-	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -c -o $@ $<
+$(OBJ)/icp_util.o: $(CSRC)/pose_host.h
 
 # the launch plan is plain C++ (tests/cpp builds the same file without HIP)
 $(OBJ)/decode_plan.o: $(CSRC)/decode_plan.cpp $(CSRC)/decode_plan.h include/ouster_hip.h

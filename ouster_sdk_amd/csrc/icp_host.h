@@ -1,6 +1,6 @@
 // icp_host.h -- the host half of point_to_point_align / point_to_plane_align (csrc/host/icp_util.cpp): validation with the
 // reference's messages, the constants of a call, the two solves behind the sums of a pass, the stop rules, and the plain C++
-// restatement behind ouster_hip_icp_align_ref / ouster_hip_icp_step_ref.  Plain C++, no HIP: the C ABI (ouster_hip_capi.hip) calls
+// restatement behind ouster_hip_icp_align_ref / ouster_hip_icp_step_ref.  Plain C++, no HIP: the C ABI (capi_icp.hip) calls
 // it before anything touches the GPU and after each pass's read-back.
 #pragma once
 #include <stddef.h>

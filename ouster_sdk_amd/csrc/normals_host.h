@@ -1,6 +1,6 @@
 // normals_host.h -- the host half of algorithm::normals (csrc/host/normals_util.cpp): validation with the reference's messages
 // and the per-call constants, the only place where acos and tan are evaluated (libm).  Plain C++, no HIP: the C ABI
-// (ouster_hip_capi.hip) calls it before anything touches the GPU and between the two kernels.
+// (capi_normals.hip) calls it before anything touches the GPU and between the two kernels.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -3,36 +3,23 @@
 // device tables and launches the kernels of ouster_hip_kernels.hip.  No compute happens
 // on the host except the one-off XYZ table construction (make_xyz_lut is a one-off in the
 // reference too: ouster_core/src/xyzlut.cpp:11-89, cached per sensor in sensor_info.cpp:260-275).
+// The entry points of a feature (images, frame_ops, pose, normals, voxel, ICP) are in capi_<feature>.hip, next to its kernels.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <fcntl.h>
-#include <map>
 #include <new>
-#include <string>
 #include <unistd.h>
-#include <vector>
 
-#include "host_pool.h"
-#include "k_frame_ops.h"
-#include "k_image.h"
-#include "k_normals.h"
-#include "k_pose.h"
-#include "k_voxel.h"
-#include "k_icp.h"
-#include "ouster_hip_dev.h"
+#include "capi_internal.h"
 
 using namespace ouster_hip_dev;
 
-namespace {
+static thread_local std::string g_err;
 
-thread_local std::string g_err;
-
+namespace ouster_hip_dev {
 int fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -42,107 +29,9 @@ int fail(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
-
-#define HIP_TRY(expr)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess)                                                           \
-            return fail(OUSTER_HIP_ERR_RUNTIME, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return 0;
-        counted_free(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = n + n / 2;
-        if (counted_malloc(&p, want) != hipSuccess) {
-            p = nullptr;
-            return -1;
-        }
-        cap = want;
-        return 0;
-    }
-    void release() {
-        counted_free(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-}  // namespace
-
 // the error channel of the plain C++ parts of the library (csrc/pose_host.h)
-namespace ouster_hip_dev {
 int fail_msg(int code, const char* msg) { return fail(code, "%s", msg); }
 }  // namespace ouster_hip_dev
-
-// k_decode variant (64-column tiles / wide tiles of 128 or 256 columns / the persistent kernel) per workload, picked by
-// timing each candidate on the first calls: which one is faster depends on how the output planes happen to be placed
-// in HBM
-struct Tune {
-    int best = -2;  // -2: still measuring; 0: narrow; 128 / 256: wide; 1000 + tile width: the persistent kernel
-    int calls = 0;
-    bool from_cache = false;   // `best` was read from the tuning cache file, not timed by this context
-    static constexpr int ROUNDS = 4, NCAND = 5, SAMPLES = NCAND * ROUNDS;
-    hipEvent_t ev[SAMPLES][2] = {};  // up to five candidates x ROUNDS consecutive launches
-    float ms[NCAND] = {0, 0, 0, 0, 0};  // fastest warm sample of each candidate
-    void destroy() {
-        for (auto& pr : ev)
-            for (hipEvent_t& e : pr)
-                if (e) (void)hipEventDestroy(e), e = nullptr;
-    }
-};
-
-struct ouster_hip_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    DevBuf state, tile_valid, offsets, luts, counts, scratch, slotmap, hdrw, osf_pixels;
-    DevBuf image_mask;                   // ouster_hip_image_dark_rows: the column masks of a batch
-    void* fops_pin = nullptr;            //   ... their page-locked staging, and the event behind its last copy
-    size_t fops_pin_cap = 0;
-    hipEvent_t fops_ev = nullptr;
-    DevBuf fops_tables;                  // ouster_hip_frame_ops_*: shift tables reduced to [0, w) / row indices of the call in flight
-    DevBuf normals_pairs;                // ouster_hip_normals: what k_normals_subtent leaves, 16 bytes per frame and return
-    bool voxel_timing = false, voxel_timed = false;   // ouster_hip_voxel_timing: events around the phases of a call
-    hipEvent_t voxel_ev[OUSTER_HIP_VOXEL_PHASES + 1] = {};
-    DevBuf voxel_ws;                     // ouster_hip_voxel_downsample: keys, table, ids, sorted indices, gathered rows, sort temporaries
-    bool icp_timing = false;             // ouster_hip_icp_timing: events around the phases of a call; icp_timed_passes: of the last one
-    uint32_t icp_timed_passes = 0;
-    bool icp_timed = false;
-    hipEvent_t icp_ev[2 + 4 * 10] = {};  //   start, after the grid, then per pass: start, after correspond, after median, after sums
-    DevBuf icp_ws;                       // ouster_hip_icp_*: the target grid, the per-row outputs of a pass, partial sums, sort temporaries
-    DevBuf user_scratch[8];              // ouster_hip_ctx_scratch: what the *_host calls and bindings stage through
-    uint32_t resident_wgs = 512;         // 2 workgroups (80 KB LDS each) per CU
-    uint32_t cus = 256;                  // compute units (k_decode_stream: one persistent workgroup each)
-    const char* last_kernel = "";        // name of the decode kernel the last ouster_hip_decode launched
-    bool state_dirty = false;            // `state` may hold leftovers (fix-up pass skipped / a failed launch)
-    std::vector<int32_t> offsets_host;   // cache key of `offsets`
-    std::vector<int32_t> shifts_host;    // pixel_shift_by_row the cached offsets were derived from
-    uint32_t shifts_w = 0;               //   ... and the frame width (the offsets are (W + x % W) % W)
-    std::vector<LutDev> luts_host;       // cache key of `luts`
-    // pageable host packet_counts go through a small pinned ring (no stream synchronisation)
-    static constexpr int RING = 4;
-    uint32_t* ring_buf[RING] = {nullptr, nullptr, nullptr, nullptr};
-    size_t ring_cap[RING] = {0, 0, 0, 0};
-    hipEvent_t ring_ev[RING] = {nullptr, nullptr, nullptr, nullptr};
-    int ring_next = 0;
-    Knobs knobs;
-    bool timing = false;
-    uint32_t timing_every = 1, timing_calls = 0;   // HIP events around every timing_every-th decode kernel (an event record costs the stream 2 - 3 us)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    size_t ev_used = 0;
-    std::map<uint64_t, Tune> tune;       // the variant tuner, by workload key (decode_plan.h)
-    // verdicts of earlier processes (ouster_hip_ctx_set_tuning_cache): workload key -> chosen variant, for THIS device and library
-    std::string tune_cache_path, tune_cache_id;
-    std::map<uint64_t, int> tune_cache;
-    const char* last_tuner = "none";     // how the last ouster_hip_decode chose its variant
-    int last_tile_cols = 0, last_tile_rows = 0;  // tile of the last k_decode launch
-};
 
 static void tune_forget(ouster_hip_ctx* c) {   // the one place the tuner's events are destroyed
     for (auto& kv : c->tune) kv.second.destroy();
@@ -343,16 +232,14 @@ void ouster_hip_ctx_destroy(ouster_hip_ctx* c) {
     c->hdrw.release();
     c->osf_pixels.release();
     c->image_mask.release();
-    c->fops_tables.release();
+    c->tables.release();
     c->normals_pairs.release();
     c->voxel_ws.release();
     c->icp_ws.release();
-    for (hipEvent_t& e : c->icp_ev)
-        if (e) (void)hipEventDestroy(e), e = nullptr;
-    for (hipEvent_t& e : c->voxel_ev)
-        if (e) (void)hipEventDestroy(e), e = nullptr;
-    if (c->fops_ev) (void)hipEventDestroy(c->fops_ev);
-    if (c->fops_pin) (void)hipHostFree(c->fops_pin);
+    c->icp_timer.destroy();
+    c->voxel_timer.destroy();
+    if (c->table_ev) (void)hipEventDestroy(c->table_ev);
+    if (c->table_pin) (void)hipHostFree(c->table_pin);
     for (auto& b : c->user_scratch) b.release();
     for (auto& p : c->ev_pool) {
         (void)hipEventDestroy(p.first);
@@ -555,10 +442,10 @@ int ouster_hip_lut_create_from_arrays(ouster_hip_ctx* ctx, const void* direction
         return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     if (w == 0 || h == 0)
         return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "lut dimensions must be greater than zero");
-    if (dtype != OUSTER_HIP_F32 && dtype != OUSTER_HIP_F64)
+    if (!float_elem(dtype))
         return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "LUT dtype must be F32 or F64");
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t hw = (size_t)w * h, es = dtype == OUSTER_HIP_F32 ? 4 : 8;
+    const size_t hw = (size_t)w * h, es = float_elem(dtype);
     ouster_hip_lut* L = new (std::nothrow) ouster_hip_lut();
     if (!L) return fail(OUSTER_HIP_ERR_RUNTIME, "out of memory");
     L->device = ctx->device;
@@ -1115,7 +1002,7 @@ int ouster_hip_destagger(ouster_hip_ctx* ctx, const void* src, void* dst, uint32
 int ouster_hip_cartesian(ouster_hip_ctx* ctx, const ouster_hip_lut* lut, const uint32_t* range,
                          void* xyz, int xyz_dtype, uint32_t n_images) {
     if (!ctx || !lut) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (xyz_dtype != OUSTER_HIP_F32 && xyz_dtype != OUSTER_HIP_F64)
+    if (!float_elem(xyz_dtype))
         return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "xyz_dtype must be F32 or F64");
     if (n_images == 0) return OUSTER_HIP_OK;
     if (!range || !xyz) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL image pointer");
@@ -1139,7 +1026,7 @@ int ouster_hip_cartesian(ouster_hip_ctx* ctx, const ouster_hip_lut* lut, const u
 int ouster_hip_dewarp(ouster_hip_ctx* ctx, const void* points, const double* poses, void* dewarped,
                       int dtype, uint32_t h, uint32_t w, uint32_t n_images) {
     if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (dtype != OUSTER_HIP_F32 && dtype != OUSTER_HIP_F64)
+    if (!float_elem(dtype))
         return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
     if (n_images == 0 || h == 0 || w == 0) return OUSTER_HIP_OK;
     if (!points || !poses || !dewarped) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
@@ -1189,35 +1076,6 @@ int ouster_hip_copy_out(ouster_hip_ctx* ctx, void* host_dst, const void* dev_src
     return OUSTER_HIP_OK;
 }
 
-namespace {
-// One host array of a *_host call: pool memory is handed to the kernel as it is, anything else gets a slot of the context's
-// grow-only scratch (inputs copied in now, outputs copied out by finish()).
-struct HostArg {
-    void* dev = nullptr;
-    void* host = nullptr;
-    size_t bytes = 0;
-    bool staged = false;
-};
-int host_arg(ouster_hip_ctx* ctx, const void* host, size_t bytes, uint32_t slot, bool is_input, HostArg& a) {
-    a.host = const_cast<void*>(host);
-    a.bytes = bytes;
-    if (ouster_hip_host_is_pinned(host, bytes)) {
-        a.dev = a.host;
-        return OUSTER_HIP_OK;
-    }
-    a.staged = true;
-    if (ctx->user_scratch[slot].ensure(bytes)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (scratch %u, %zu bytes)", slot, bytes);
-    a.dev = ctx->user_scratch[slot].p;
-    if (is_input) HIP_TRY(hipMemcpyAsync(a.dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return OUSTER_HIP_OK;
-}
-int host_finish(ouster_hip_ctx* ctx, const HostArg& out) {
-    if (out.staged) HIP_TRY(hipMemcpyAsync(out.host, out.dev, out.bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return OUSTER_HIP_OK;
-}
-}  // namespace
-
 int ouster_hip_destagger_host(ouster_hip_ctx* ctx, const void* src, void* dst, uint32_t h, uint32_t w,
                               uint32_t elem_bytes, const int32_t* shifts, uint32_t n_shifts, int inverse) {
     if (!ctx || !shifts) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -1226,595 +1084,49 @@ int ouster_hip_destagger_host(ouster_hip_ctx* ctx, const void* src, void* dst, u
     if (!src || !dst || elem_bytes == 0) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "bad image arguments");
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)h * w * elem_bytes;
-    HostArg in, out;
-    int rc = host_arg(ctx, src, bytes, 0, true, in);
-    if (rc == OUSTER_HIP_OK) rc = host_arg(ctx, dst, bytes, 1, false, out);
-    if (rc != OUSTER_HIP_OK) return rc;
+    Staging st(ctx);
     // in place (src == dst) in the reference copies rows through each other: not a supported call there either; go through scratch
-    if (in.dev == out.dev) {
-        if (ctx->user_scratch[1].ensure(bytes)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (scratch)");
-        out.dev = ctx->user_scratch[1].p;
-        out.staged = true;
-    }
-    rc = ouster_hip_destagger(ctx, in.dev, out.dev, h, w, elem_bytes, shifts, n_shifts, inverse, 1);
+    const auto in = st.input(src, bytes), out = st.output(dst, bytes, src == dst);
+    int rc = st.stage();
     if (rc != OUSTER_HIP_OK) return rc;
-    return host_finish(ctx, out);
+    rc = ouster_hip_destagger(ctx, st.dev(in), st.dev(out), h, w, elem_bytes, shifts, n_shifts, inverse, 1);
+    if (rc != OUSTER_HIP_OK) return rc;
+    return st.finish();
 }
 
 int ouster_hip_cartesian_host(ouster_hip_ctx* ctx, const ouster_hip_lut* lut, const uint32_t* range, void* xyz,
                               int xyz_dtype) {
     if (!ctx || !lut) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (xyz_dtype != OUSTER_HIP_F32 && xyz_dtype != OUSTER_HIP_F64)
+    if (!float_elem(xyz_dtype))
         return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "xyz_dtype must be F32 or F64");
     const size_t npx = (size_t)lut->w * lut->h;
     if (npx == 0) return OUSTER_HIP_OK;
     if (!range || !xyz) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL image pointer");
     HIP_TRY(hipSetDevice(ctx->device));
-    HostArg in, out;
-    int rc = host_arg(ctx, range, npx * 4, 0, true, in);
-    if (rc == OUSTER_HIP_OK) rc = host_arg(ctx, xyz, npx * 3 * (xyz_dtype == OUSTER_HIP_F64 ? 8 : 4), 1, false, out);
+    Staging st(ctx);
+    const auto in = st.input(range, npx * 4), out = st.output(xyz, npx * 3 * float_elem(xyz_dtype));
+    int rc = st.stage();
     if (rc != OUSTER_HIP_OK) return rc;
-    rc = ouster_hip_cartesian(ctx, lut, (const uint32_t*)in.dev, out.dev, xyz_dtype, 1);
+    rc = ouster_hip_cartesian(ctx, lut, (const uint32_t*)st.dev(in), st.dev(out), xyz_dtype, 1);
     if (rc != OUSTER_HIP_OK) return rc;
-    return host_finish(ctx, out);
+    return st.finish();
 }
 
 int ouster_hip_dewarp_host(ouster_hip_ctx* ctx, const void* points, const double* poses, void* dewarped, int dtype,
                            uint32_t h, uint32_t w) {
     if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (dtype != OUSTER_HIP_F32 && dtype != OUSTER_HIP_F64) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
+    if (!float_elem(dtype)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
     if (h == 0 || w == 0) return OUSTER_HIP_OK;
     if (!points || !poses || !dewarped) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t pbytes = (size_t)h * w * 3 * (dtype == OUSTER_HIP_F64 ? 8 : 4);
-    HostArg in, po, out;
-    int rc = host_arg(ctx, points, pbytes, 0, true, in);
-    if (rc == OUSTER_HIP_OK) rc = host_arg(ctx, poses, (size_t)w * 128, 2, true, po);
-    if (rc == OUSTER_HIP_OK) rc = host_arg(ctx, dewarped, pbytes, 1, false, out);
+    const size_t pbytes = (size_t)h * w * 3 * float_elem(dtype);
+    Staging st(ctx);
+    const auto in = st.input(points, pbytes), po = st.input(poses, (size_t)w * 128), out = st.output(dewarped, pbytes);
+    int rc = st.stage();
     if (rc != OUSTER_HIP_OK) return rc;
-    rc = ouster_hip_dewarp(ctx, in.dev, (const double*)po.dev, out.dev, dtype, h, w, 1);
+    rc = ouster_hip_dewarp(ctx, st.dev(in), (const double*)st.dev(po), st.dev(out), dtype, h, w, 1);
     if (rc != OUSTER_HIP_OK) return rc;
-    return host_finish(ctx, out);
-}
-
-// ---- display images (k_image.hip) ----------------------------------------------------------------
-namespace {
-size_t image_elem(int t) {
-    switch (t) {
-        case OUSTER_HIP_U8: return 1;
-        case OUSTER_HIP_U16: return 2;
-        case OUSTER_HIP_U32: case OUSTER_HIP_F32: return 4;
-        case OUSTER_HIP_F64: return 8;
-        default: return 0;
-    }
-}
-// shared argument checks; fills what every image kernel needs.  Returns 1 when there is nothing to do.
-int image_args(ouster_hip_ctx* ctx, const void* planes, int in_type, int out_type, uint32_t n_images, uint32_t h, uint32_t w,
-               size_t image_stride, ImageArgs& a) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (out_type != OUSTER_HIP_F32 && out_type != OUSTER_HIP_F64)
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "out_type must be F32 or F64");
-    if (in_type != OUSTER_HIP_U8 && in_type != OUSTER_HIP_U16 && in_type != OUSTER_HIP_U32 && in_type != out_type)
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "in_type must be U8, U16, U32 or out_type");
-    if (n_images == 0 || h == 0 || w == 0) return 1;
-    if (n_images > 65535u) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at most 65535 images per call");
-    if ((uint64_t)h * w > (1ull << 31)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "image larger than 2^31 elements");
-    if (!planes) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL image pointer");
-    if (image_stride && image_stride < (size_t)h * w) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "image_stride smaller than an image");
-    a = ImageArgs{};
-    a.in = planes;
-    a.in_stride = image_stride ? image_stride : (size_t)h * w;
-    a.n_images = n_images;
-    a.h = h;
-    a.w = w;
-    const size_t vb = std::min<size_t>(16, 4 * image_elem(in_type));
-    a.vec = ((uintptr_t)planes % vb == 0) && (a.in_stride % 4 == 0 || n_images == 1);
-    return OUSTER_HIP_OK;
-}
-}  // namespace
-
-int ouster_hip_image_dark_rows(ouster_hip_ctx* ctx, const void* planes, int in_type, int out_type, uint32_t n_images,
-                               uint32_t h, uint32_t w, size_t image_stride, void* medians, uint32_t* n_cols) {
-    ImageArgs a;
-    const int rc = image_args(ctx, planes, in_type, out_type, n_images, h, w, image_stride, a);
-    if (rc) return rc > 0 ? OUSTER_HIP_OK : rc;
-    if (w > IMAGE_MAX_W_DARK) return fail(OUSTER_HIP_ERR_UNSUPPORTED, "dark rows: images wider than %u columns", IMAGE_MAX_W_DARK);
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (h < 2) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dark rows need at least two rows");
-    if (!medians) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "medians is NULL");
-    const size_t words = (w + 63) / 64;
-    if (ctx->image_mask.ensure((size_t)n_images * words * 8)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (column masks)");
-    a.col_mask = (uint64_t*)ctx->image_mask.p;
-    a.medians = medians;
-    a.n_cols = n_cols;
-    a.vec = a.vec && (w % 4 == 0);
-    HIP_TRY(launch_image_dark_rows(a, in_type, out_type, ctx->stream));
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_image_percentiles(ouster_hip_ctx* ctx, const void* planes, int in_type, int out_type, uint32_t n_images,
-                                 uint32_t h, uint32_t w, size_t image_stride, const void* dark, double lo_percentile,
-                                 double hi_percentile, uint32_t* n, void* lo_hi) {
-    ImageArgs a;
-    const int rc = image_args(ctx, planes, in_type, out_type, n_images, h, w, image_stride, a);
-    if (rc) return rc > 0 ? OUSTER_HIP_OK : rc;
-    if (!n || !lo_hi) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL output pointer");
-    if (!(lo_percentile >= 0) || !(hi_percentile >= 0) || !(lo_percentile + hi_percentile < 1))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "percentiles must be >= 0 and sum to less than 1");
-    HIP_TRY(hipSetDevice(ctx->device));
-    a.dark = dark;
-    a.lo_percentile = lo_percentile;
-    a.hi_percentile = hi_percentile;
-    a.n_positive = n;
-    a.lo_hi = lo_hi;
-    HIP_TRY(launch_image_percentiles(a, in_type, out_type, ctx->stream));
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_image_apply(ouster_hip_ctx* ctx, const void* planes, int in_type, void* out, int out_type, uint32_t n_images,
-                           uint32_t h, uint32_t w, size_t in_stride, size_t out_stride, const void* dark,
-                           const ouster_hip_image_map* maps) {
-    ImageArgs a;
-    const int rc = image_args(ctx, planes, in_type, out_type, n_images, h, w, in_stride, a);
-    if (rc) return rc > 0 ? OUSTER_HIP_OK : rc;
-    if (!out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "out is NULL");
-    if (out_stride && out_stride < (size_t)h * w) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "out_stride smaller than an image");
-    if (out == planes && (in_type != out_type || (out_stride ? out_stride : (size_t)h * w) != a.in_stride))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "in place needs equal types and strides");
-    HIP_TRY(hipSetDevice(ctx->device));
-    a.out = out;
-    a.out_stride = out_stride ? out_stride : (size_t)h * w;
-    a.vec = a.vec && ((uintptr_t)out % 16 == 0) && (a.out_stride % 4 == 0 || n_images == 1);
-    a.dark = dark;
-    a.maps = maps;
-    HIP_TRY(launch_image_apply(a, in_type, out_type, ctx->stream));
-    return OUSTER_HIP_OK;
-}
-
-// One host image: scratch slot 0 holds a foreign image, slot 2 the few numbers that go out, slot 3 those that come in.
-int ouster_hip_image_dark_rows_host(ouster_hip_ctx* ctx, const void* image, int dtype, uint32_t h, uint32_t w, void* medians,
-                                    uint32_t* n_cols) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    const size_t es = (dtype == OUSTER_HIP_F32 || dtype == OUSTER_HIP_F64) ? image_elem(dtype) : 0;
-    if (!es) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
-    if (h < 2 || w == 0) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dark rows need at least two rows");
-    if (!image || !medians || !n_cols) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HostArg in;
-    int rc = host_arg(ctx, image, (size_t)h * w * es, 0, true, in);
-    if (rc != OUSTER_HIP_OK) return rc;
-    const size_t mbytes = (size_t)(h - 1) * es;
-    if (ctx->user_scratch[2].ensure(mbytes + 8)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (scratch)");
-    uint8_t* d = (uint8_t*)ctx->user_scratch[2].p;
-    rc = ouster_hip_image_dark_rows(ctx, in.dev, dtype, dtype, 1, h, w, 0, d + 8, (uint32_t*)d);
-    if (rc != OUSTER_HIP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(medians, d + 8, mbytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(n_cols, d, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_image_percentiles_host(ouster_hip_ctx* ctx, const void* image, int dtype, uint32_t h, uint32_t w,
-                                      const void* dark, double lo_percentile, double hi_percentile, uint32_t* n,
-                                      void* lo_hi) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    const size_t es = (dtype == OUSTER_HIP_F32 || dtype == OUSTER_HIP_F64) ? image_elem(dtype) : 0;
-    if (!es) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
-    if (!image || !n || !lo_hi || h == 0 || w == 0) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "bad image arguments");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HostArg in;
-    int rc = host_arg(ctx, image, (size_t)h * w * es, 0, true, in);
-    if (rc != OUSTER_HIP_OK) return rc;
-    if (ctx->user_scratch[2].ensure(8 + 2 * es)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (scratch)");
-    uint8_t* d = (uint8_t*)ctx->user_scratch[2].p;
-    void* d_dark = nullptr;
-    if (dark) {
-        if (ctx->user_scratch[3].ensure((size_t)h * es)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (scratch)");
-        d_dark = ctx->user_scratch[3].p;
-        HIP_TRY(hipMemcpyAsync(d_dark, dark, (size_t)h * es, hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = ouster_hip_image_percentiles(ctx, in.dev, dtype, dtype, 1, h, w, 0, d_dark, lo_percentile, hi_percentile, (uint32_t*)d, d + 8);
-    if (rc != OUSTER_HIP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(n, d, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(lo_hi, d + 8, 2 * es, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_image_apply_host(ouster_hip_ctx* ctx, void* image, int dtype, uint32_t h, uint32_t w, const void* dark,
-                                const ouster_hip_image_map* map) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    const size_t es = (dtype == OUSTER_HIP_F32 || dtype == OUSTER_HIP_F64) ? image_elem(dtype) : 0;
-    if (!es) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
-    if (h == 0 || w == 0) return OUSTER_HIP_OK;
-    if (!image) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL image pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HostArg io;
-    int rc = host_arg(ctx, image, (size_t)h * w * es, 0, true, io);
-    if (rc != OUSTER_HIP_OK) return rc;
-    const size_t dbytes = dark ? (size_t)h * es : 0, doff = sizeof(ouster_hip_image_map);
-    if (ctx->user_scratch[3].ensure(doff + dbytes)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (scratch)");
-    uint8_t* d = (uint8_t*)ctx->user_scratch[3].p;
-    ouster_hip_image_map m{};
-    if (map) m = *map;
-    else m.use_dark = 1;
-    HIP_TRY(hipMemcpyAsync(d, &m, sizeof m, hipMemcpyHostToDevice, ctx->stream));   // pageable source: staged before the call returns
-    if (dark) HIP_TRY(hipMemcpyAsync(d + doff, dark, dbytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = ouster_hip_image_apply(ctx, io.dev, dtype, io.dev, dtype, 1, h, w, 0, 0, dark ? d + doff : nullptr,
-                                (const ouster_hip_image_map*)d);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return host_finish(ctx, io);
-}
-
-// ---- frame_ops (k_frame_ops.hip) ------------------------------------------------------------------
-namespace {
-// A small host table (reduced shifts, row indices) -> ctx->fops_tables, safe by construction for back-to-back asynchronous
-// calls: the source is copied into page-locked staging owned by the context, the staging is reused only after the event behind
-// its last copy has completed, and the device buffer grows only on an idle stream.
-int fops_upload(ouster_hip_ctx* ctx, const void* src, size_t bytes) {
-    if (ctx->fops_ev) HIP_TRY(hipEventSynchronize(ctx->fops_ev));
-    else HIP_TRY(hipEventCreateWithFlags(&ctx->fops_ev, hipEventDisableTiming));
-    if (bytes > ctx->fops_pin_cap) {
-        if (ctx->fops_pin) (void)hipHostFree(ctx->fops_pin);
-        ctx->fops_pin = nullptr;
-        ctx->fops_pin_cap = 0;
-        HIP_TRY(hipHostMalloc(&ctx->fops_pin, bytes * 2, hipHostMallocDefault));
-        ctx->fops_pin_cap = bytes * 2;
-    }
-    if (bytes > ctx->fops_tables.cap) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));   // a kernel in flight may still read the old table
-        if (ctx->fops_tables.ensure(bytes)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (frame_ops tables)");
-    }
-    std::memcpy(ctx->fops_pin, src, bytes);
-    HIP_TRY(hipMemcpyAsync(ctx->fops_tables.p, ctx->fops_pin, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->fops_ev, ctx->stream));
-    return OUSTER_HIP_OK;
-}
-
-size_t fops_elem(int t) {
-    switch (t) {
-        case OUSTER_HIP_U8: case OUSTER_HIP_I8: return 1;
-        case OUSTER_HIP_U16: case OUSTER_HIP_I16: return 2;
-        case OUSTER_HIP_U32: case OUSTER_HIP_I32: case OUSTER_HIP_F32: return 4;
-        case OUSTER_HIP_U64: case OUSTER_HIP_I64: case OUSTER_HIP_F64: return 8;
-        default: return 0;
-    }
-}
-const char* fops_type_name(int t) {
-    static const char* names[] = {"VOID", "UINT8", "UINT16", "UINT32", "UINT64", "INT8", "INT16", "INT32", "INT64", "FLOAT32", "FLOAT64"};
-    return (t >= 0 && t <= 10) ? names[t] : "?";
-}
-// shared checks of the three entry points; returns 1 when there is nothing to do
-int fops_shape(ouster_hip_ctx* ctx, uint32_t n_planes, uint32_t n_images, uint32_t h, uint32_t w) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (n_images > 65535u) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at most 65535 images per call");
-    if ((uint64_t)h * w > (1ull << 31)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "image larger than 2^31 elements");
-    return (n_planes == 0 || n_images == 0 || h == 0 || w == 0) ? 1 : OUSTER_HIP_OK;
-}
-// the planes of one call -> the launch records; every `invalid` is checked before the first launch
-int fops_planes(const ouster_hip_fops_plane* planes, uint32_t n_planes, uint32_t h, uint32_t w, std::vector<FopsPlane>& out,
-                bool clouds_allowed = false) {
-    if (!planes) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "planes is NULL");
-    out.resize(n_planes);
-    for (uint32_t i = 0; i < n_planes; ++i) {
-        const ouster_hip_fops_plane& p = planes[i];
-        FopsPlane& o = out[i];
-        if (p.type == OUSTER_HIP_FOPS_XYZ_F32 || p.type == OUSTER_HIP_FOPS_XYZ_F64) {
-            const uint32_t scalar = p.type == OUSTER_HIP_FOPS_XYZ_F64 ? 8 : 4;
-            if (!clouds_allowed) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: a cloud can only be invalidated", i);
-            if (p.invalid != 0 || p.twin) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: a cloud takes invalid == 0 and no twin", i);
-            if (!p.data || (uintptr_t)p.data % scalar) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: NULL or misaligned pointer", i);
-            if (p.image_stride && p.image_stride < (size_t)h * w) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: image_stride smaller than an image", i);
-            o = FopsPlane{};
-            o.data = p.data;
-            o.stride = p.image_stride ? p.image_stride : (size_t)h * w;
-            o.elem = 3 * scalar;
-            o.type = p.type;
-            continue;
-        }
-        o.elem = (uint32_t)fops_elem(p.type);
-        if (!o.elem) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: unsupported element type %d", i, p.type);
-        const int rc = ouster_hip_frame_ops_invalid_bits(p.type, p.invalid, &o.invalid_bits);
-        if (rc != OUSTER_HIP_OK) return rc;
-        if (!p.data || (uintptr_t)p.data % o.elem || (uintptr_t)p.twin % o.elem)
-            return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: NULL or misaligned pointer", i);
-        if (p.image_stride && p.image_stride < (size_t)h * w)
-            return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: image_stride smaller than an image", i);
-        o.data = p.data;
-        o.twin = p.twin;
-        o.stride = p.image_stride ? p.image_stride : (size_t)h * w;
-        o.type = p.type;
-    }
-    return OUSTER_HIP_OK;
-}
-}  // namespace
-
-int ouster_hip_frame_ops_invalid_bits(int type, double invalid, uint64_t* bits) {
-    if (!bits) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "bits is NULL");
-    *bits = 0;
-    bool ok = true;
-    const double t = std::trunc(invalid);
-    auto put = [&](auto v) { std::memcpy(bits, &v, sizeof v); };
-    switch (type) {
-        case OUSTER_HIP_U8: ok = t >= 0 && t <= 255.0; if (ok) put((uint8_t)t); break;
-        case OUSTER_HIP_U16: ok = t >= 0 && t <= 65535.0; if (ok) put((uint16_t)t); break;
-        case OUSTER_HIP_U32: ok = t >= 0 && t <= 4294967295.0; if (ok) put((uint32_t)t); break;
-        case OUSTER_HIP_U64: ok = t >= 0 && t < 18446744073709551616.0; if (ok) put((uint64_t)t); break;
-        case OUSTER_HIP_I8: ok = t >= -128.0 && t <= 127.0; if (ok) put((int8_t)t); break;
-        case OUSTER_HIP_I16: ok = t >= -32768.0 && t <= 32767.0; if (ok) put((int16_t)t); break;
-        case OUSTER_HIP_I32: ok = t >= -2147483648.0 && t <= 2147483647.0; if (ok) put((int32_t)t); break;
-        case OUSTER_HIP_I64: ok = t >= -9223372036854775808.0 && t < 9223372036854775808.0; if (ok) put((int64_t)t); break;
-        case OUSTER_HIP_F32: ok = !std::isfinite(invalid) || std::fabs(invalid) <= 3.4028234663852886e38; if (ok) put((float)invalid); break;
-        case OUSTER_HIP_F64: put(invalid); break;
-        default: return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "unsupported element type %d", type);
-    }
-    if (!ok) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "invalid == %g does not fit a field of type %s", invalid, fops_type_name(type));
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_frame_ops_clip(ouster_hip_ctx* ctx, const ouster_hip_fops_plane* planes, uint32_t n_planes,
-                              uint32_t n_images, uint32_t h, uint32_t w, double lower, double upper) {
-    std::vector<FopsPlane> pl;
-    int rc = fops_planes(planes, n_planes, h, w, pl);   // also when there is nothing to do: a bad `invalid` is an error
-    if (rc != OUSTER_HIP_OK && n_planes) return rc;
-    rc = fops_shape(ctx, n_planes, n_images, h, w);
-    if (rc) return rc > 0 ? OUSTER_HIP_OK : rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    for (uint32_t p0 = 0; p0 < n_planes; p0 += FOPS_MAX_PLANES) {
-        FopsClipArgs a{};
-        a.n_planes = std::min<uint32_t>(FOPS_MAX_PLANES, n_planes - p0);
-        std::copy(pl.begin() + p0, pl.begin() + p0 + a.n_planes, a.planes);
-        a.n_images = n_images;
-        a.hw = h * w;
-        a.lower = lower;
-        a.upper = upper;
-        HIP_TRY(launch_fops_clip(a, ctx->stream));
-    }
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_frame_ops_invalidate(ouster_hip_ctx* ctx, const ouster_hip_fops_pred* pred,
-                                    const ouster_hip_fops_plane* planes, uint32_t n_planes, uint32_t n_images,
-                                    uint32_t h, uint32_t w) {
-    if (!pred) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "pred is NULL");
-    std::vector<FopsPlane> pl;
-    int rc = fops_planes(planes, n_planes, h, w, pl, true);
-    if (rc != OUSTER_HIP_OK && n_planes) return rc;
-    rc = fops_shape(ctx, n_planes, n_images, h, w);
-    if (rc < 0) return rc;
-    const bool nothing = rc > 0;
-    FopsInvalidateArgs a{};
-    a.kind = pred->kind;
-    a.src_type = pred->src_type;
-    a.src = pred->src;
-    a.src_stride = pred->src_stride ? pred->src_stride : (size_t)h * w;
-    a.n_masks = pred->n_masks;
-    a.axis = pred->axis;
-    a.lower = pred->lower;
-    a.upper = pred->upper;
-    a.lo = pred->lo;
-    a.hi = pred->hi;
-    bool need_shifts = false;
-    for (const FopsPlane& p : pl) need_shifts = need_shifts || p.twin != nullptr;
-    switch (pred->kind) {
-        case OUSTER_HIP_FOPS_PRED_KEY:
-            if (!fops_elem(pred->src_type)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "unsupported key element type %d", pred->src_type);
-            if (!nothing && (!pred->src || (uintptr_t)pred->src % fops_elem(pred->src_type))) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL or misaligned key plane");
-            break;
-        case OUSTER_HIP_FOPS_PRED_ROWS:
-        case OUSTER_HIP_FOPS_PRED_COLS: {
-            const uint32_t size = pred->kind == OUSTER_HIP_FOPS_PRED_ROWS ? h : w;
-            if (pred->lo > pred->hi || pred->hi > size)
-                return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "index range [%u, %u) must lie in [0, %u]", pred->lo, pred->hi, size);
-            need_shifts = need_shifts || pred->kind == OUSTER_HIP_FOPS_PRED_COLS;
-            break;
-        }
-        case OUSTER_HIP_FOPS_PRED_MASK:
-            if (pred->n_masks == 0 || (!nothing && !pred->src)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "mask predicate without masks");
-            break;
-        case OUSTER_HIP_FOPS_PRED_XYZ:
-            if (pred->src_type != OUSTER_HIP_F32 && pred->src_type != OUSTER_HIP_F64) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "xyz type must be F32 or F64");
-            if (pred->axis > 2) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "axis == %u must be in the range [0, 2]", pred->axis);
-            if (!nothing && (!pred->src || (uintptr_t)pred->src % fops_elem(pred->src_type))) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL or misaligned point cloud");
-            break;
-        default:
-            return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "unknown predicate kind %d", pred->kind);
-    }
-    if (need_shifts && (!pred->shifts || pred->n_shift_tables == 0))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "this call needs pixel_shift_by_row tables");
-    if (nothing) return OUSTER_HIP_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    a.n_images = n_images;
-    a.h = h;
-    a.w = w;
-    if (need_shifts) {
-        // (W + x % W) % W on the host, once per row: the kernel wraps a column with one conditional subtraction
-        const size_t n = (size_t)pred->n_shift_tables * h;
-        std::vector<uint32_t> red(n);
-        for (size_t i = 0; i < n; ++i) red[i] = (uint32_t)((((int64_t)pred->shifts[i] % (int64_t)w) + w) % w);
-        const int urc = fops_upload(ctx, red.data(), n * 4);
-        if (urc != OUSTER_HIP_OK) return urc;
-        a.shifts = (const uint32_t*)ctx->fops_tables.p;
-        a.n_tables = pred->n_shift_tables;
-    }
-    // a key that is also a target must be read before it is written, for EVERY target of the pixel: where the list needs
-    // more than one launch the key plane goes into the last one
-    if (pred->kind == OUSTER_HIP_FOPS_PRED_KEY && n_planes > FOPS_MAX_PLANES)
-        std::stable_partition(pl.begin(), pl.end(), [&](const FopsPlane& p) { return p.data != pred->src; });
-    for (uint32_t p0 = 0; p0 < n_planes; p0 += FOPS_MAX_PLANES) {
-        a.n_planes = std::min<uint32_t>(FOPS_MAX_PLANES, n_planes - p0);
-        std::copy(pl.begin() + p0, pl.begin() + p0 + a.n_planes, a.planes);
-        HIP_TRY(launch_fops_invalidate(a, ctx->stream));
-    }
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_frame_ops_select_rows(ouster_hip_ctx* ctx, const void* const* src, void* const* dst,
-                                     const uint32_t* elem_bytes, uint32_t n_planes, uint32_t n_images, uint32_t h,
-                                     uint32_t w, const uint32_t* indices, uint32_t n_sel) {
-    int rc = fops_shape(ctx, n_planes, n_images, h, w);
-    if (rc < 0) return rc;
-    if (n_sel > 65535u) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at most 65535 rows per call");
-    if (n_sel && !indices) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "indices is NULL");
-    for (uint32_t i = 0; i < n_sel; ++i)
-        if (indices[i] >= h) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "row index %u must be in the range [0, %u)", indices[i], h);
-    if (rc > 0 || n_sel == 0) return OUSTER_HIP_OK;
-    if (!src || !dst || !elem_bytes) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    for (uint32_t p = 0; p < n_planes; ++p) {
-        const uint32_t e = elem_bytes[p];
-        if (e != 1 && e != 2 && e != 4 && e != 8) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: elem_bytes must be 1, 2, 4 or 8", p);
-        if (!src[p] || !dst[p] || (uintptr_t)src[p] % e || (uintptr_t)dst[p] % e) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: NULL or misaligned pointer", p);
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int urc = fops_upload(ctx, indices, (size_t)n_sel * 4);
-    if (urc != OUSTER_HIP_OK) return urc;
-    for (uint32_t p0 = 0; p0 < n_planes; p0 += FOPS_MAX_PLANES) {
-        FopsSelectArgs a{};
-        a.n_planes = std::min<uint32_t>(FOPS_MAX_PLANES, n_planes - p0);
-        for (uint32_t i = 0; i < a.n_planes; ++i) {
-            a.src[i] = src[p0 + i];
-            a.dst[i] = dst[p0 + i];
-            a.elem[i] = elem_bytes[p0 + i];
-        }
-        a.n_images = n_images;
-        a.h = h;
-        a.w = w;
-        a.n_sel = n_sel;
-        a.indices = (const uint32_t*)ctx->fops_tables.p;
-        HIP_TRY(launch_fops_select_rows(a, ctx->stream));
-    }
-    return OUSTER_HIP_OK;
-}
-
-namespace {
-// The planes of a *_host call: pool memory stays where it is, every other plane gets a 16-byte aligned piece of scratch `slot`.
-struct HostPlanes {
-    std::vector<void*> dev;
-    std::vector<size_t> bytes;
-    std::vector<bool> staged;
-    int stage(ouster_hip_ctx* ctx, const void* const* host, const size_t* nbytes, uint32_t n, uint32_t slot, bool copy_in) {
-        dev.assign(n, nullptr);
-        bytes.assign(nbytes, nbytes + n);
-        staged.assign(n, false);
-        size_t total = 0;
-        std::vector<size_t> off(n, 0);
-        for (uint32_t i = 0; i < n; ++i) {
-            if (!host[i]) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: NULL pointer", i);
-            if (ouster_hip_host_is_pinned(host[i], nbytes[i])) {
-                dev[i] = const_cast<void*>(host[i]);
-                continue;
-            }
-            staged[i] = true;
-            off[i] = total;
-            total += (nbytes[i] + 15) & ~(size_t)15;
-        }
-        if (total && ctx->user_scratch[slot].ensure(total)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (scratch %u, %zu bytes)", slot, total);
-        for (uint32_t i = 0; i < n; ++i) {
-            if (!staged[i]) continue;
-            dev[i] = (uint8_t*)ctx->user_scratch[slot].p + off[i];
-            if (copy_in) HIP_TRY(hipMemcpyAsync(dev[i], host[i], nbytes[i], hipMemcpyHostToDevice, ctx->stream));
-        }
-        return OUSTER_HIP_OK;
-    }
-    int finish(ouster_hip_ctx* ctx, void* const* host) {
-        for (size_t i = 0; i < dev.size(); ++i)
-            if (staged[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return OUSTER_HIP_OK;
-    }
-};
-int fops_host_planes(ouster_hip_ctx* ctx, const ouster_hip_fops_plane* planes, uint32_t n_planes, uint32_t h, uint32_t w,
-                     std::vector<ouster_hip_fops_plane>& dev_planes, std::vector<void*>& host, HostPlanes& hp) {
-    if (!ctx || !planes) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    std::vector<size_t> nbytes(n_planes);
-    host.resize(n_planes);
-    for (uint32_t i = 0; i < n_planes; ++i) {
-        uint64_t bits;
-        if (!fops_elem(planes[i].type)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: unsupported element type %d", i, planes[i].type);
-        const int rc = ouster_hip_frame_ops_invalid_bits(planes[i].type, planes[i].invalid, &bits);
-        if (rc != OUSTER_HIP_OK) return rc;
-        if (planes[i].twin) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: a host call takes no twin plane", i);
-        nbytes[i] = (size_t)h * w * fops_elem(planes[i].type);
-        host[i] = planes[i].data;
-    }
-    if ((uint64_t)h * w == 0 || n_planes == 0) return 1;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int rc = hp.stage(ctx, host.data(), nbytes.data(), n_planes, 0, true);
-    if (rc != OUSTER_HIP_OK) return rc;
-    dev_planes.assign(planes, planes + n_planes);
-    for (uint32_t i = 0; i < n_planes; ++i) {
-        dev_planes[i].data = hp.dev[i];
-        dev_planes[i].image_stride = 0;
-    }
-    return OUSTER_HIP_OK;
-}
-}  // namespace
-
-int ouster_hip_frame_ops_clip_host(ouster_hip_ctx* ctx, const ouster_hip_fops_plane* planes, uint32_t n_planes, uint32_t h,
-                                   uint32_t w, double lower, double upper) {
-    std::vector<ouster_hip_fops_plane> dp;
-    std::vector<void*> host;
-    HostPlanes hp;
-    int rc = fops_host_planes(ctx, planes, n_planes, h, w, dp, host, hp);
-    if (rc) return rc > 0 ? OUSTER_HIP_OK : rc;
-    rc = ouster_hip_frame_ops_clip(ctx, dp.data(), n_planes, 1, h, w, lower, upper);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return hp.finish(ctx, host.data());
-}
-
-int ouster_hip_frame_ops_invalidate_host(ouster_hip_ctx* ctx, const ouster_hip_fops_pred* pred,
-                                         const ouster_hip_fops_plane* planes, uint32_t n_planes, uint32_t h, uint32_t w) {
-    if (!pred) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "pred is NULL");
-    std::vector<ouster_hip_fops_plane> dp;
-    std::vector<void*> host;
-    HostPlanes hp;
-    int rc = fops_host_planes(ctx, planes, n_planes, h, w, dp, host, hp);
-    if (rc) return rc > 0 ? OUSTER_HIP_OK : rc;
-    ouster_hip_fops_pred dpred = *pred;
-    dpred.src_stride = 0;
-    size_t sbytes = 0;
-    switch (pred->kind) {
-        case OUSTER_HIP_FOPS_PRED_KEY: sbytes = (size_t)h * w * fops_elem(pred->src_type); break;
-        case OUSTER_HIP_FOPS_PRED_MASK: sbytes = (size_t)h * w; dpred.n_masks = 1; break;
-        case OUSTER_HIP_FOPS_PRED_XYZ: sbytes = (size_t)h * w * 3 * (pred->src_type == OUSTER_HIP_F64 ? 8 : 4); break;
-        default: break;
-    }
-    if (sbytes) {
-        if (!pred->src) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "predicate source is NULL");
-        dpred.src = nullptr;
-        for (uint32_t i = 0; i < n_planes; ++i)   // the key among the targets: the same device image
-            if (host[i] == pred->src && hp.bytes[i] == sbytes) dpred.src = hp.dev[i];
-        if (!dpred.src) {
-            HostArg src;
-            rc = host_arg(ctx, pred->src, sbytes, 1, true, src);
-            if (rc != OUSTER_HIP_OK) return rc;
-            dpred.src = src.dev;
-        }
-    }
-    rc = ouster_hip_frame_ops_invalidate(ctx, &dpred, dp.data(), n_planes, 1, h, w);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return hp.finish(ctx, host.data());
-}
-
-int ouster_hip_frame_ops_select_rows_host(ouster_hip_ctx* ctx, const void* const* src, void* const* dst,
-                                          const uint32_t* elem_bytes, uint32_t n_planes, uint32_t h, uint32_t w,
-                                          const uint32_t* indices, uint32_t n_sel) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (n_planes == 0 || h == 0 || w == 0 || n_sel == 0) return ouster_hip_frame_ops_select_rows(ctx, src, dst, elem_bytes, n_planes, 1, h, w, indices, n_sel);
-    if (!src || !dst || !elem_bytes) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    std::vector<size_t> sb(n_planes), db(n_planes);
-    for (uint32_t p = 0; p < n_planes; ++p) {
-        sb[p] = (size_t)h * w * elem_bytes[p];
-        db[p] = (size_t)n_sel * w * elem_bytes[p];
-    }
-    HostPlanes in, out;
-    int rc = in.stage(ctx, src, sb.data(), n_planes, 0, true);
-    if (rc == OUSTER_HIP_OK) rc = out.stage(ctx, dst, db.data(), n_planes, 1, false);
-    if (rc != OUSTER_HIP_OK) return rc;
-    rc = ouster_hip_frame_ops_select_rows(ctx, in.dev.data(), out.dev.data(), elem_bytes, n_planes, 1, h, w, indices, n_sel);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return out.finish(ctx, dst);
+    return st.finish();
 }
 
 // ---- range-gated, compacting frame dewarp ------------------------------------------------------
@@ -1846,7 +1158,7 @@ static int dewarp_frames_impl(ouster_hip_ctx* ctx, const ouster_hip_lut* const* 
                               uint32_t* frame_idxs, uint32_t* col_idxs, uint64_t* timestamps_ns,
                               uint64_t capacity, uint64_t* frame_offsets, const uint16_t* gate_counts) {
     if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (dtype != OUSTER_HIP_F32 && dtype != OUSTER_HIP_F64)
+    if (!float_elem(dtype))
         return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
     if (!luts || n_luts == 0) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at least one LUT is required");
     for (uint32_t i = 0; i < n_luts; ++i) {
@@ -2023,669 +1335,6 @@ int ouster_hip_last_decode_tile(ouster_hip_ctx* ctx, int* tile_cols, int* tile_r
     if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
     if (tile_cols) *tile_cols = ctx->last_tile_cols;
     if (tile_rows) *tile_rows = ctx->last_tile_rows;
-    return OUSTER_HIP_OK;
-}
-
-// ---- interp_pose / transform (k_pose.hip, host/pose_util.cpp) --------------------------------------
-namespace {
-// validated known poses -> the table and the known times on the device, [k - 1][24] + [k] doubles in ctx->fops_tables
-int pose_tables(ouster_hip_ctx* ctx, const std::vector<double>& host, uint32_t k, PoseInterpArgs& a) {
-    const int rc = fops_upload(ctx, host.data(), host.size() * 8);
-    if (rc != OUSTER_HIP_OK) return rc;
-    a.segments = (const double*)ctx->fops_tables.p;
-    a.x_known = a.segments + (size_t)(k - 1) * POSE_SEG_DOUBLES;
-    a.k = k;
-    return OUSTER_HIP_OK;
-}
-int pose_known_host(const double* x_known, const double* poses_known, uint32_t k, std::vector<double>& host) {
-    if (const char* msg = pose_validate_known(x_known, poses_known, k)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", msg);
-    host.resize((size_t)(k - 1) * POSE_SEG_DOUBLES + k);
-    for (uint32_t i = 0; i + 1 < k; ++i)
-        pose_segment(x_known[i], poses_known + 16 * (size_t)i, x_known[i + 1], poses_known + 16 * (size_t)(i + 1),
-                     host.data() + (size_t)POSE_SEG_DOUBLES * i);
-    std::copy(x_known, x_known + k, host.begin() + (size_t)(k - 1) * POSE_SEG_DOUBLES);
-    return OUSTER_HIP_OK;
-}
-int pose_pair_host(double t0, const double* x0, double t1, const double* x1, std::vector<double>& host) {
-    if (const char* msg = pose_validate_pair(t0, t1)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", msg);
-    if (!x0 || !x1) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pose");
-    host.assign(POSE_SEG_DOUBLES + 2, 0.0);   // one segment; with k == 2 the known times select nothing
-    pose_segment(t0, x0, t1, x1, host.data());
-    host[POSE_SEG_DOUBLES] = t0;
-    host[POSE_SEG_DOUBLES + 1] = t1;
-    return OUSTER_HIP_OK;
-}
-int pose_interp_launch(ouster_hip_ctx* ctx, const std::vector<double>& host, uint32_t k, PoseInterpArgs& a) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (a.dtype != OUSTER_HIP_F32 && a.dtype != OUSTER_HIP_F64) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
-    if (a.n == 0) return OUSTER_HIP_OK;
-    if (a.n > (1ull << 38)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at most 2^38 poses per call");
-    if (!a.out || (!a.x && (!a.timestamp || !a.status))) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    if (((uintptr_t)a.out | (uintptr_t)a.pose_rows) & 15) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "pose output is not 16-byte aligned");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int rc = pose_tables(ctx, host, k, a);
-    if (rc != OUSTER_HIP_OK) return rc;
-    a.direct_stores = ctx->knobs.pose_direct ? 1 : 0;
-    HIP_TRY(launch_pose_interp(a, ctx->stream));
-    return OUSTER_HIP_OK;
-}
-int pose_interp_host(ouster_hip_ctx* ctx, const double* x_interp, uint64_t n, const std::vector<double>& table, uint32_t k,
-                     int dtype, void* poses_out) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (dtype != OUSTER_HIP_F32 && dtype != OUSTER_HIP_F64) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
-    if (n == 0) return OUSTER_HIP_OK;
-    if (!x_interp || !poses_out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    char msg[160];
-    if (pose_validate_interp(x_interp, n, msg, sizeof msg)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", msg);
-    HIP_TRY(hipSetDevice(ctx->device));
-    HostArg in, out;
-    int rc = host_arg(ctx, x_interp, n * 8, 0, true, in);
-    if (rc == OUSTER_HIP_OK) rc = host_arg(ctx, poses_out, n * 16 * (dtype == OUSTER_HIP_F64 ? 8 : 4), 1, false, out);
-    if (rc != OUSTER_HIP_OK) return rc;
-    PoseInterpArgs a{};
-    a.x = (const double*)in.dev;
-    a.n = n;
-    a.dtype = dtype;
-    a.out = out.dev;
-    rc = pose_interp_launch(ctx, table, k, a);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return host_finish(ctx, out);
-}
-int pose_columns(ouster_hip_ctx* ctx, const uint64_t* timestamp, const uint32_t* status, uint32_t n_frames, uint32_t w,
-                 const std::vector<double>& table, uint32_t k, double* poses, float* pose_rows) {
-    PoseInterpArgs a{};
-    a.timestamp = timestamp;
-    a.status = status;
-    a.n = (uint64_t)n_frames * w;
-    a.dtype = OUSTER_HIP_F64;
-    a.out = poses;
-    a.pose_rows = pose_rows;
-    return pose_interp_launch(ctx, table, k, a);
-}
-}  // namespace
-
-int ouster_hip_pose_validate(const double* x_known, const double* poses_known, uint32_t k, const double* x_interp, uint64_t n) {
-    if (const char* msg = pose_validate_known(x_known, poses_known, k)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", msg);
-    char msg[160];
-    if (x_interp && pose_validate_interp(x_interp, n, msg, sizeof msg)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", msg);
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_interp_pose(ouster_hip_ctx* ctx, const double* x_interp_dev, uint64_t n, const double* x_known,
-                           const double* poses_known, uint32_t k, int dtype, void* poses_out_dev) {
-    std::vector<double> table;
-    const int rc = pose_known_host(x_known, poses_known, k, table);
-    if (rc != OUSTER_HIP_OK) return rc;
-    PoseInterpArgs a{};
-    a.x = x_interp_dev;
-    a.n = n;
-    a.dtype = dtype;
-    a.out = poses_out_dev;
-    if (n && !x_interp_dev) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    return pose_interp_launch(ctx, table, k, a);
-}
-
-int ouster_hip_interp_pose_host(ouster_hip_ctx* ctx, const double* x_interp, uint64_t n, const double* x_known,
-                                const double* poses_known, uint32_t k, int dtype, void* poses_out) {
-    std::vector<double> table;
-    const int rc = pose_known_host(x_known, poses_known, k, table);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return pose_interp_host(ctx, x_interp, n, table, k, dtype, poses_out);
-}
-
-int ouster_hip_interp_pose_pair_host(ouster_hip_ctx* ctx, const double* x_interp, uint64_t n, double t0, const double* x0,
-                                     double t1, const double* x1, int dtype, void* poses_out) {
-    std::vector<double> table;
-    const int rc = pose_pair_host(t0, x0, t1, x1, table);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return pose_interp_host(ctx, x_interp, n, table, 2, dtype, poses_out);
-}
-
-int ouster_hip_interp_pose_columns(ouster_hip_ctx* ctx, const uint64_t* timestamp_dev, const uint32_t* status_dev,
-                                   uint32_t n_frames, uint32_t w, const double* x_known, const double* poses_known,
-                                   uint32_t k, double* poses_dev, float* pose_rows_dev) {
-    std::vector<double> table;
-    const int rc = pose_known_host(x_known, poses_known, k, table);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return pose_columns(ctx, timestamp_dev, status_dev, n_frames, w, table, k, poses_dev, pose_rows_dev);
-}
-
-int ouster_hip_interp_pose_pair_columns(ouster_hip_ctx* ctx, const uint64_t* timestamp_dev, const uint32_t* status_dev,
-                                        uint32_t n_frames, uint32_t w, double t0, const double* x0, double t1,
-                                        const double* x1, double* poses_dev, float* pose_rows_dev) {
-    std::vector<double> table;
-    const int rc = pose_pair_host(t0, x0, t1, x1, table);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return pose_columns(ctx, timestamp_dev, status_dev, n_frames, w, table, 2, poses_dev, pose_rows_dev);
-}
-
-int ouster_hip_transform(ouster_hip_ctx* ctx, const void* points_dev, const double* pose16, void* out_dev, int dtype,
-                         uint64_t n) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (dtype != OUSTER_HIP_F32 && dtype != OUSTER_HIP_F64) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
-    if (!pose16) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "pose is NULL");
-    if (n == 0) return OUSTER_HIP_OK;
-    if (n > (1ull << 38)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at most 2^38 points per call");
-    if (!points_dev || !out_dev) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    PoseTransformArgs a{};
-    a.points = points_dev;
-    a.out = out_dev;
-    std::copy(pose16, pose16 + 16, a.pose);
-    a.n = n;
-    a.dtype = dtype;
-    HIP_TRY(launch_pose_transform(a, ctx->stream));
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_transform_host(ouster_hip_ctx* ctx, const void* points, const double* pose16, void* out, int dtype, uint64_t n) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (dtype != OUSTER_HIP_F32 && dtype != OUSTER_HIP_F64) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
-    if (!pose16) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "pose is NULL");
-    if (n == 0) return OUSTER_HIP_OK;
-    if (!points || !out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n * 3 * (dtype == OUSTER_HIP_F64 ? 8 : 4);
-    HostArg in, o;
-    int rc = host_arg(ctx, points, bytes, 0, true, in);
-    if (rc == OUSTER_HIP_OK) rc = host_arg(ctx, out, bytes, 1, false, o);
-    if (rc != OUSTER_HIP_OK) return rc;
-    rc = ouster_hip_transform(ctx, in.dev, pose16, o.dev, dtype, n);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return host_finish(ctx, o);
-}
-
-// ---- algorithm::normals (k_normals.hip, host/normals_util.cpp) -------------------------------------
-namespace {
-int normals_validate(const ouster_hip_normals_desc* d) {
-    if (!d) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "desc is NULL");
-    const bool dual = d->xyz2 || d->range2;
-    if (const char* msg = normals_validate_shapes(d->h, d->w, d->xyz_rows, dual, d->xyz2_rows, d->range2_h, d->range2_w,
-                                                  d->sensor_origins ? d->n_origins : d->w))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", msg);
-    if (const char* msg = normals_validate_params(d->min_angle_of_incidence_rad, d->target_distance_m))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", msg);
-    if (d->xyz_dtype != OUSTER_HIP_F32 && d->xyz_dtype != OUSTER_HIP_F64) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "xyz_dtype must be F32 or F64");
-    return OUSTER_HIP_OK;
-}
-
-// d: every array in device memory
-int normals_device(ouster_hip_ctx* ctx, const ouster_hip_normals_desc* d) {
-    const bool dual = d->xyz2 || d->range2;
-    if (!d->xyz || !d->range || !d->normals || (dual && (!d->xyz2 || !d->range2 || !d->normals2)))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    const uint32_t n_ret = dual ? 2 : 1;
-    const uint64_t rows = (uint64_t)d->n_frames * n_ret;
-    if (rows > 65535) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at most 65535 frames x returns per call");
-    if ((uint64_t)d->n_frames * d->h * d->w > (1ull << 40)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at most 2^40 pixels per call");
-    if ((d->h + NORMALS_TILE_H - 1) / NORMALS_TILE_H > 65535) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at most 262140 rows");
-    HIP_TRY(hipSetDevice(ctx->device));
-    NormalsArgs a{};
-    a.xyz[0] = d->xyz, a.xyz[1] = d->xyz2;
-    a.range[0] = d->range, a.range[1] = d->range2;
-    a.out[0] = d->normals, a.out[1] = d->normals2;
-    a.f32 = d->xyz_dtype == OUSTER_HIP_F32;
-    a.n_frames = d->n_frames, a.h = d->h, a.w = d->w, a.n_ret = n_ret;
-    a.origins = d->sensor_origins;
-    a.poses = d->sensor_origins ? nullptr : d->poses;
-    // the last column of every sensor_to_body; with poses and no matrix: identity's
-    const bool with_s2b = !d->sensor_origins && (d->poses || d->sensor_to_body);
-    a.n_s2b = with_s2b ? (d->sensor_to_body ? std::max(d->n_sensor_to_body, 1u) : 1u) : 0u;
-    // Radii beyond the image are cut off at max(h, w), with the same result.  Vertical: the loop leaves at the first radius above
-    // both max_up and max_down, which are below h, so a range of h or more never reaches its last radius.  Horizontal: by radius w
-    // every pixel of the row has been visited with both signs; later radii revisit them at equal error, which never replaces the
-    // best one (strict <), and the thin flag can only have been cleared already, so best, thin and good are constant from radius
-    // w on -- and the reference's last-radius rule (accept the closest candidate under the threshold at radius ==
-    // pixel_search_range) tests that constant state, whichever radius at or beyond w is the last.
-    a.pixel_search_range = std::min(d->pixel_search_range, std::max(d->h, d->w));
-    a.staggered_out = d->pixel_shift_by_row && d->staggered_output;
-    // table: the constants [rows][4] f64, the sensor_to_body columns [n_s2b][4] f64, then the shifts reduced to [0, w); the first
-    // upload carries the constants as zeros
-    const size_t cbytes = (size_t)rows * 4 * 8, mbytes = (size_t)a.n_s2b * 4 * 8, sbytes = d->pixel_shift_by_row ? (size_t)d->h * 4 : 0;
-    std::vector<uint8_t> table(cbytes + mbytes + sbytes, 0);
-    for (uint32_t m = 0; m < a.n_s2b; ++m) {
-        double* col = reinterpret_cast<double*>(table.data() + cbytes) + 4 * (size_t)m;
-        col[3] = 1.0;
-        if (d->sensor_to_body)
-            for (int r = 0; r < 4; ++r) col[r] = d->sensor_to_body[16 * (size_t)m + 4 * r + 3];
-    }
-    if (sbytes) {
-        uint32_t* red = reinterpret_cast<uint32_t*>(table.data() + cbytes + mbytes);
-        const int64_t w = d->w;
-        for (uint32_t u = 0; u < d->h; ++u) red[u] = (uint32_t)(((int64_t)d->pixel_shift_by_row[u] % w + w) % w);
-    }
-    int rc = fops_upload(ctx, table.data(), table.size());
-    if (rc != OUSTER_HIP_OK) return rc;
-    a.consts = (const double*)ctx->fops_tables.p;
-    a.s2b = mbytes ? (const double*)((const uint8_t*)ctx->fops_tables.p + cbytes) : nullptr;
-    a.shifts = sbytes ? (const uint32_t*)((const uint8_t*)ctx->fops_tables.p + cbytes + mbytes) : nullptr;
-    if (ctx->normals_pairs.cap < rows * sizeof(NormalsPair)) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->normals_pairs.ensure(rows * sizeof(NormalsPair))) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (normals)");
-    }
-    a.pairs = (NormalsPair*)ctx->normals_pairs.p;
-    HIP_TRY(launch_normals_subtent(a, ctx->stream));
-    std::vector<NormalsPair> pairs(rows);
-    HIP_TRY(hipMemcpyAsync(pairs.data(), a.pairs, rows * sizeof(NormalsPair), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    double* k = reinterpret_cast<double*>(table.data());
-    for (uint32_t f = 0; f < d->n_frames; ++f) {
-        ouster_hip_normals_consts c0, c;
-        const NormalsPair& p0 = pairs[(size_t)f * n_ret];
-        normals_constants(d->w, d->h, d->min_angle_of_incidence_rad, d->target_distance_m, p0.rows != 0, p0.dot, p0.rows, &c0);
-        for (uint32_t r = 0; r < n_ret; ++r) {
-            c = c0;
-            if (r == 1 && !(c0.subtent > 0.0)) {   // the override of the dual form is not taken: the second return's own columns
-                const NormalsPair& p1 = pairs[(size_t)f * n_ret + 1];
-                normals_constants(d->w, d->h, d->min_angle_of_incidence_rad, d->target_distance_m, p1.rows != 0, p1.dot, p1.rows, &c);
-            }
-            double* row = k + ((size_t)f * n_ret + r) * 4;
-            row[0] = c.px_res_h, row[1] = c.px_res_v, row[2] = c.tan_safe, row[3] = c.target_sq;
-        }
-    }
-    rc = fops_upload(ctx, table.data(), table.size());
-    if (rc != OUSTER_HIP_OK) return rc;
-    a.consts = (const double*)ctx->fops_tables.p;
-    a.s2b = mbytes ? (const double*)((const uint8_t*)ctx->fops_tables.p + cbytes) : nullptr;
-    a.shifts = sbytes ? (const uint32_t*)((const uint8_t*)ctx->fops_tables.p + cbytes + mbytes) : nullptr;
-    HIP_TRY(launch_normals(a, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return OUSTER_HIP_OK;
-}
-}  // namespace
-
-int ouster_hip_normals(ouster_hip_ctx* ctx, const ouster_hip_normals_desc* desc) {
-    const int rc = normals_validate(desc);
-    if (rc != OUSTER_HIP_OK) return rc;
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if ((uint64_t)desc->n_frames * desc->h * desc->w == 0) return OUSTER_HIP_OK;
-    return normals_device(ctx, desc);
-}
-
-int ouster_hip_normals_host(ouster_hip_ctx* ctx, const ouster_hip_normals_desc* desc) {
-    int rc = normals_validate(desc);
-    if (rc != OUSTER_HIP_OK) return rc;
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    const size_t px = (size_t)desc->n_frames * desc->h * desc->w;
-    if (px == 0) return OUSTER_HIP_OK;
-    const bool dual = desc->xyz2 || desc->range2;
-    if (!desc->xyz || !desc->range || !desc->normals || (dual && (!desc->xyz2 || !desc->range2 || !desc->normals2)))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t es = desc->xyz_dtype == OUSTER_HIP_F32 ? 4 : 8;
-    std::vector<const void*> in = {desc->xyz, desc->range};
-    std::vector<size_t> in_bytes = {px * 3 * es, px * 4};
-    if (dual) in.push_back(desc->xyz2), in_bytes.push_back(px * 3 * es), in.push_back(desc->range2), in_bytes.push_back(px * 4);
-    const bool with_poses = !desc->sensor_origins && desc->poses;
-    if (desc->sensor_origins) in.push_back(desc->sensor_origins), in_bytes.push_back((size_t)desc->w * 24);
-    if (with_poses) in.push_back(desc->poses), in_bytes.push_back((size_t)desc->n_frames * desc->w * 128);
-    std::vector<void*> out = {desc->normals};
-    std::vector<size_t> out_bytes = {px * 24};
-    if (dual) out.push_back(desc->normals2), out_bytes.push_back(px * 24);
-    HostPlanes hin, hout;
-    rc = hin.stage(ctx, in.data(), in_bytes.data(), (uint32_t)in.size(), 0, true);
-    if (rc == OUSTER_HIP_OK) rc = hout.stage(ctx, out.data(), out_bytes.data(), (uint32_t)out.size(), 1, false);
-    if (rc != OUSTER_HIP_OK) return rc;
-    ouster_hip_normals_desc d = *desc;
-    size_t i = 0;
-    d.xyz = hin.dev[i++], d.range = (const uint32_t*)hin.dev[i++];
-    if (dual) d.xyz2 = hin.dev[i++], d.range2 = (const uint32_t*)hin.dev[i++];
-    if (desc->sensor_origins) d.sensor_origins = (const double*)hin.dev[i++];
-    if (with_poses) d.poses = (const double*)hin.dev[i++];
-    d.normals = (double*)hout.dev[0];
-    if (dual) d.normals2 = (double*)hout.dev[1];
-    rc = normals_device(ctx, &d);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return hout.finish(ctx, out.data());
-}
-
-// ---- voxel down-sampling (k_voxel.hip, host/voxel_util.cpp) ------------------------------------------
-namespace {
-// everything but the device: NULL / dtype / stride / table_log2; 1: nothing to do (n == 0)
-int voxel_validate_call(const ouster_hip_voxel_desc* d, uint64_t* n_out) {
-    if (!d || !n_out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    *n_out = 0;
-    if (d->n == 0 && !d->normals) return 1;
-    if (const char* msg = voxel_validate(d)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", msg);
-    if (d->dtype != OUSTER_HIP_F32 && d->dtype != OUSTER_HIP_F64) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
-    if (d->row_stride && d->row_stride < d->cols) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "row_stride is smaller than cols");
-    if (d->table_log2 && (d->table_log2 > 31 || (1ull << d->table_log2) <= d->n))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "voxel_downsample: 2^table_log2 must exceed n (table_log2 <= 31)");
-    if (d->n == 0) return 1;
-    if (!d->points || (d->out_capacity && (!d->out || (d->normals && !d->out_normals)))) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    return OUSTER_HIP_OK;
-}
-
-// d: every array in device memory, validated, a form the GPU takes
-int voxel_device(ouster_hip_ctx* ctx, const ouster_hip_voxel_desc* d, uint64_t* n_out) {
-    if (d->n > VOXEL_MAX_POINTS) return fail(OUSTER_HIP_ERR_UNSUPPORTED, "voxel_downsample: more than 2^30 points");
-    HIP_TRY(hipSetDevice(ctx->device));
-    VoxelArgs a{};
-    a.points = d->points, a.normals = d->normals;
-    a.n = (uint32_t)d->n, a.cols = d->cols;
-    a.stride = d->row_stride ? d->row_stride : d->cols;
-    a.f32 = d->dtype == OUSTER_HIP_F32;
-    a.form = voxel_form(d);
-    a.inv = 1.0 / d->voxel_size;
-    a.min_pts = d->min_pts_threshold;
-    a.out = d->out, a.out_normals = d->out_normals, a.out_capacity = d->out_capacity;
-    uint32_t log2 = d->table_log2;
-    if (!log2)
-        for (log2 = 1; (1ull << log2) < 2 * d->n; ++log2) {}
-    a.table_mask = (uint32_t)((1ull << log2) - 1);
-    const bool folds = a.form == VOXEL_FORM_AVERAGE || a.form == VOXEL_FORM_NORMALS;
-    size_t temp_bytes = 0;
-    HIP_TRY(voxel_temp_bytes(a.n, &temp_bytes));
-    // the workspace, every piece 256-byte aligned
-    const size_t n = a.n;
-    size_t total = 0;
-    auto take = [&total](size_t bytes) {
-        const size_t at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t o_hdr = take(sizeof(VoxelHeader)), o_keys = take(n * sizeof(VoxelKey)), o_table = take(((size_t)a.table_mask + 1) * 4),
-                 o_slot = take(n * 4), o_first = take(n * 4), o_first_id = take(n * 4), o_vid = take(n * 4), o_idx = take(n * 4),
-                 o_svid = take(n * 4), o_sidx = take(n * 4), o_begin = take(n * 4), o_end = take(n * 4),
-                 o_keep = take(folds ? n * 4 : 0), o_pos = take(folds ? n * 4 : 0),
-                 o_rows = take(folds ? n * 8 * (a.form == VOXEL_FORM_NORMALS ? 6 : a.cols) : 0), o_temp = take(temp_bytes);
-    if (ctx->voxel_ws.cap < total) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->voxel_ws.ensure(total)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (voxel workspace, %zu bytes)", total);
-    }
-    uint8_t* ws = (uint8_t*)ctx->voxel_ws.p;
-    a.hdr = (VoxelHeader*)(ws + o_hdr), a.keys = (VoxelKey*)(ws + o_keys), a.table = (int32_t*)(ws + o_table);
-    a.slot = (uint32_t*)(ws + o_slot), a.first = (uint32_t*)(ws + o_first), a.first_id = (uint32_t*)(ws + o_first_id);
-    a.vid = (uint32_t*)(ws + o_vid), a.idx = (uint32_t*)(ws + o_idx), a.svid = (uint32_t*)(ws + o_svid), a.sidx = (uint32_t*)(ws + o_sidx);
-    a.seg_begin = (uint32_t*)(ws + o_begin), a.seg_end = (uint32_t*)(ws + o_end);
-    a.keep = (uint32_t*)(ws + o_keep), a.pos = (uint32_t*)(ws + o_pos), a.rows = (double*)(ws + o_rows);
-    ctx->voxel_timed = false;
-    HIP_TRY(voxel_run(a, ws + o_temp, temp_bytes, ctx->stream, ctx->voxel_timing ? ctx->voxel_ev : nullptr));
-    VoxelHeader hdr{};
-    HIP_TRY(hipMemcpyAsync(&hdr, a.hdr, sizeof hdr, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->voxel_timed = ctx->voxel_timing;
-    if (hdr.status == VOXEL_STATUS_TABLE) return fail(OUSTER_HIP_ERR_RUNTIME, "voxel_downsample: hash table exhausted");
-    if (hdr.status) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", VOXEL_MSG_GRID);
-    *n_out = hdr.n_out;
-    if (hdr.n_out > d->out_capacity) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "voxel_downsample: out_capacity is too small");
-    return OUSTER_HIP_OK;
-}
-}  // namespace
-
-int ouster_hip_voxel_timing(ouster_hip_ctx* ctx, int on) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (on)
-        for (hipEvent_t& e : ctx->voxel_ev)
-            if (!e) HIP_TRY(hipEventCreate(&e));
-    ctx->voxel_timing = on != 0;
-    ctx->voxel_timed = false;
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_voxel_phase_ms(ouster_hip_ctx* ctx, float* ms) {
-    if (!ctx || !ms) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!ctx->voxel_timed) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "voxel_downsample: no timed call (ouster_hip_voxel_timing)");
-    for (int k = 0; k < OUSTER_HIP_VOXEL_PHASES; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], ctx->voxel_ev[k], ctx->voxel_ev[k + 1]));
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_voxel_downsample(ouster_hip_ctx* ctx, const ouster_hip_voxel_desc* desc, uint64_t* n_out) {
-    const int rc = voxel_validate_call(desc, n_out);
-    if (rc != OUSTER_HIP_OK) return rc == 1 ? OUSTER_HIP_OK : rc;
-    if (voxel_form(desc) == VOXEL_FORM_HOST)
-        return fail(OUSTER_HIP_ERR_UNSUPPORTED, "voxel_downsample: FIRST_N_POINT / RANDOM with max_points_per_voxel > 1 run on the host (the _host form)");
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    return voxel_device(ctx, desc, n_out);
-}
-
-int ouster_hip_voxel_downsample_host(ouster_hip_ctx* ctx, const ouster_hip_voxel_desc* desc, uint64_t* n_out) {
-    int rc = voxel_validate_call(desc, n_out);
-    if (rc != OUSTER_HIP_OK) return rc == 1 ? OUSTER_HIP_OK : rc;
-    if (voxel_form(desc) == VOXEL_FORM_HOST) return ouster_hip_voxel_downsample_ref(desc, n_out);
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (desc->n > VOXEL_MAX_POINTS) return fail(OUSTER_HIP_ERR_UNSUPPORTED, "voxel_downsample: more than 2^30 points");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t es = desc->dtype == OUSTER_HIP_F32 ? 4 : 8, stride = desc->row_stride ? desc->row_stride : desc->cols;
-    const bool wn = desc->normals != nullptr;
-    std::vector<const void*> in = {desc->points};
-    std::vector<size_t> in_bytes = {((size_t)(desc->n - 1) * stride + desc->cols) * es};
-    if (wn) in.push_back(desc->normals), in_bytes.push_back((size_t)desc->n * 24);
-    // a result of no rows still needs somewhere to point
-    static double none[3];
-    std::vector<void*> out = {desc->out_capacity ? (void*)desc->out : (void*)none};
-    std::vector<size_t> out_bytes = {(size_t)desc->out_capacity * desc->cols * 8};
-    if (wn) out.push_back(desc->out_capacity ? (void*)desc->out_normals : (void*)none), out_bytes.push_back((size_t)desc->out_capacity * 24);
-    HostPlanes hin, hout;
-    rc = hin.stage(ctx, in.data(), in_bytes.data(), (uint32_t)in.size(), 0, true);
-    // foreign output memory gets scratch that is copied back only after success: a call that refuses leaves the caller's array alone
-    if (rc == OUSTER_HIP_OK) rc = hout.stage(ctx, out.data(), out_bytes.data(), (uint32_t)out.size(), 1, false);
-    if (rc != OUSTER_HIP_OK) return rc;
-    ouster_hip_voxel_desc d = *desc;
-    d.points = hin.dev[0];
-    if (wn) d.normals = (const double*)hin.dev[1];
-    d.out = (double*)hout.dev[0];
-    if (wn) d.out_normals = (double*)hout.dev[1];
-    rc = voxel_device(ctx, &d, n_out);
-    if (rc != OUSTER_HIP_OK) return rc;
-    // only the rows of the result travel back
-    hout.bytes[0] = (size_t)*n_out * desc->cols * 8;
-    if (wn) hout.bytes[1] = (size_t)*n_out * 24;
-    return hout.finish(ctx, out.data());
-}
-
-// ---- ICP: point_to_point_align / point_to_plane_align (k_icp.hip, host/icp_util.cpp) -------------------
-namespace {
-struct IcpCall {
-    IcpArgs a{};
-    VoxelArgs va{};
-    uint8_t* temp = nullptr;
-    size_t temp_bytes = 0;
-    IcpMethod method = ICP_POINT;
-};
-
-// what every entry point refuses before a GPU is looked at; 1: fewer than 20 rows on a side (the guess is the answer)
-int icp_validate_call(const ouster_hip_icp_desc* d) {
-    if (!d) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (const char* msg = icp_validate(d)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", msg);
-    if (d->n_source > ICP_MAX_ROWS || d->n_target > ICP_MAX_ROWS) return fail(OUSTER_HIP_ERR_UNSUPPORTED, "icp: more than 2^30 rows");
-    return d->n_source < ICP_MIN_POINTS || d->n_target < ICP_MIN_POINTS ? 1 : OUSTER_HIP_OK;
-}
-
-void icp_guess_is_the_answer(ouster_hip_icp_desc* d) {
-    memcpy(d->pose, d->initial_guess, sizeof d->pose);
-    d->iterations = 0, d->solved = 0, d->correspondences = 0;
-}
-
-// d: every array in device memory, validated, at least 20 rows a side.  Lays the workspace out; launches nothing
-int icp_prepare(ouster_hip_ctx* ctx, const ouster_hip_icp_desc* d, IcpCall& c) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    IcpArgs& a = c.a;
-    c.method = icp_method(d);
-    a.src = d->source_points, a.tgt = d->target_points, a.src_n = d->source_normals, a.tgt_n = d->target_normals;
-    a.src_stride = d->source_stride ? d->source_stride : 3, a.tgt_stride = d->target_stride ? d->target_stride : 3;
-    a.src_n_stride = d->source_normal_stride ? d->source_normal_stride : 3, a.tgt_n_stride = d->target_normal_stride ? d->target_normal_stride : 3;
-    a.n_src = (uint32_t)d->n_source, a.n_tgt = (uint32_t)d->n_target;
-    a.f32 = d->dtype == OUSTER_HIP_F32, a.plane = c.method == ICP_PLANE;
-    a.inv = 1.0 / d->max_corr_dist;
-    a.max_d2 = d->max_corr_dist * d->max_corr_dist;
-    a.max_corr_dist = d->max_corr_dist;
-    a.cos_gate = a.plane ? icp_cos_gate(d->max_normal_angle_deg) : 0.0;
-    uint32_t log2 = 1;
-    while ((1ull << log2) < 2 * d->n_target) ++log2;
-    a.table_mask = (uint32_t)((1ull << log2) - 1);
-    HIP_TRY(icp_temp_bytes(a.n_src, a.n_tgt, &c.temp_bytes));
-    const size_t nt = a.n_tgt, ns = a.n_src, slots = (size_t)a.table_mask + 1;
-    size_t total = 0;
-    auto take = [&total](size_t bytes) {
-        const size_t at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t o_rb = take(sizeof(IcpReadback)), o_keys = take(nt * sizeof(VoxelKey)), o_table = take(slots * 4), o_slot = take(nt * 4),
-                 o_first = take(nt * 4), o_first_id = take(nt * 4), o_vid = take(nt * 4), o_idx = take(nt * 4), o_svid = take(nt * 4),
-                 o_sidx = take(nt * 4), o_begin = take(nt * 4), o_end = take(nt * 4), o_slots = take(slots * sizeof(IcpSlot)),
-                 o_slot_end = take(slots * 4), o_rows = take(nt * 8 * (a.plane ? 6 : 3)), o_nn = take(ns * 4), o_r = take(ns * 8),
-                 o_key = take(ns * 8), o_key_sorted = take(ns * 8), o_flag = take(ns * 4), o_xq = take(ns * 48),
-                 o_partials = take((size_t)icp_chunks(a.n_src) * OUSTER_HIP_ICP_SUMS * 8), o_temp = take(c.temp_bytes);
-    if (ctx->icp_ws.cap < total) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->icp_ws.ensure(total)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (icp workspace, %zu bytes)", total);
-    }
-    uint8_t* ws = (uint8_t*)ctx->icp_ws.p;
-    a.rb = (IcpReadback*)(ws + o_rb), a.keys = (VoxelKey*)(ws + o_keys), a.table = (int32_t*)(ws + o_table);
-    a.first_id = (uint32_t*)(ws + o_first_id), a.svid = (uint32_t*)(ws + o_svid), a.sidx = (uint32_t*)(ws + o_sidx);
-    a.seg_begin = (uint32_t*)(ws + o_begin), a.seg_end = (uint32_t*)(ws + o_end);
-    a.slots = (IcpSlot*)(ws + o_slots), a.slot_end = (uint32_t*)(ws + o_slot_end), a.rows = (double*)(ws + o_rows);
-    a.nn = (int32_t*)(ws + o_nn), a.r = (double*)(ws + o_r), a.key = (uint64_t*)(ws + o_key), a.key_sorted = (uint64_t*)(ws + o_key_sorted);
-    a.flag = (uint32_t*)(ws + o_flag), a.xq = (double*)(ws + o_xq), a.partials = (double*)(ws + o_partials);
-    c.temp = ws + o_temp;
-    // the target side as the launchers of k_voxel.h see it
-    VoxelArgs& v = c.va;
-    v.n = a.n_tgt, v.hdr = &a.rb->grid, v.keys = a.keys, v.table = a.table, v.table_mask = a.table_mask;
-    v.slot = (uint32_t*)(ws + o_slot), v.first = (uint32_t*)(ws + o_first), v.first_id = a.first_id;
-    v.vid = (uint32_t*)(ws + o_vid), v.idx = (uint32_t*)(ws + o_idx), v.svid = a.svid, v.sidx = a.sidx;
-    v.seg_begin = a.seg_begin, v.seg_end = a.seg_end;
-    return OUSTER_HIP_OK;
-}
-
-// one pass from `pose` and its read-back; the grid's refusals come with the first one
-int icp_pass(ouster_hip_ctx* ctx, IcpCall& c, const double* pose, IcpReadback& rb, hipEvent_t* ev) {
-    memcpy(c.a.pose, pose, sizeof c.a.pose);
-    if (ev) HIP_TRY(hipEventRecord(ev[0], ctx->stream));
-    HIP_TRY(icp_pass_run(c.a, c.temp, c.temp_bytes, ctx->stream, ev ? ev + 1 : nullptr));
-    HIP_TRY(hipMemcpyAsync(&rb, c.a.rb, sizeof rb, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (rb.grid.status) return fail(OUSTER_HIP_ERR_RUNTIME, "icp: hash table exhausted");
-    if (rb.pass.status) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "%s", icp_msg_grid(c.method));
-    return OUSTER_HIP_OK;
-}
-
-// d: every array in device memory, validated, at least 20 rows a side
-int icp_device(ouster_hip_ctx* ctx, ouster_hip_icp_desc* d) {
-    IcpCall c;
-    int rc = icp_prepare(ctx, d, c);
-    if (rc != OUSTER_HIP_OK) return rc;
-    const bool timing = ctx->icp_timing;
-    ctx->icp_timed = false;
-    if (timing) HIP_TRY(hipEventRecord(ctx->icp_ev[0], ctx->stream));
-    HIP_TRY(icp_grid_run(c.a, c.va, c.temp, c.temp_bytes, ctx->stream));
-    if (timing) HIP_TRY(hipEventRecord(ctx->icp_ev[1], ctx->stream));
-    double pose[16];
-    memcpy(pose, d->initial_guess, sizeof pose);
-    uint32_t iterations = 0, solved = 0;
-    uint64_t count = 0;
-    for (uint32_t it = 0; it < ICP_MAX_ITERATIONS; ++it) {
-        IcpReadback rb{};
-        rc = icp_pass(ctx, c, pose, rb, timing ? ctx->icp_ev + 2 + 4 * it : nullptr);
-        if (rc != OUSTER_HIP_OK) return rc;
-        ++iterations;
-        count = rb.pass.count;
-        solved |= count >= ICP_MIN_POINTS;
-        double next[16];
-        bool stop = true;
-        icp_finish_pass(c.method, count, rb.pass.sums, rb.pass.centroid_x, rb.pass.centroid_q, pose, next, &stop);
-        memcpy(pose, next, sizeof pose);
-        if (stop) break;
-    }
-    memcpy(d->pose, solved ? pose : d->initial_guess, sizeof pose);
-    d->iterations = iterations, d->solved = solved, d->correspondences = count;
-    ctx->icp_timed = timing;
-    ctx->icp_timed_passes = iterations;
-    return OUSTER_HIP_OK;
-}
-}  // namespace
-
-uint32_t ouster_hip_icp_chunk_rows(void) { return ICP_CHUNK; }
-
-int ouster_hip_icp_timing(ouster_hip_ctx* ctx, int on) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (on)
-        for (hipEvent_t& e : ctx->icp_ev)
-            if (!e) HIP_TRY(hipEventCreate(&e));
-    ctx->icp_timing = on != 0;
-    ctx->icp_timed = false;
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_icp_phase_ms(ouster_hip_ctx* ctx, float* ms) {
-    if (!ctx || !ms) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!ctx->icp_timed) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "icp: no timed call (ouster_hip_icp_timing)");
-    for (int k = 0; k < OUSTER_HIP_ICP_PHASES; ++k) ms[k] = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms[0], ctx->icp_ev[0], ctx->icp_ev[1]));
-    for (uint32_t it = 0; it < ctx->icp_timed_passes; ++it)
-        for (int k = 0; k < 3; ++k) {
-            float t = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&t, ctx->icp_ev[2 + 4 * it + k], ctx->icp_ev[2 + 4 * it + k + 1]));
-            ms[1 + k] += t;
-        }
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_icp_align(ouster_hip_ctx* ctx, ouster_hip_icp_desc* desc) {
-    const int rc = icp_validate_call(desc);
-    if (rc < 0) return rc;
-    if (rc == 1) return icp_guess_is_the_answer(desc), OUSTER_HIP_OK;
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    return icp_device(ctx, desc);
-}
-
-int ouster_hip_icp_step(ouster_hip_ctx* ctx, const ouster_hip_icp_desc* desc, const double* pose16, ouster_hip_icp_step_out* out) {
-    if (!pose16 || !out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = icp_validate_call(desc);
-    if (rc < 0) return rc;
-    if (rc == 1) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "icp_step: fewer than 20 rows");
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    IcpCall c;
-    rc = icp_prepare(ctx, desc, c);
-    if (rc != OUSTER_HIP_OK) return rc;
-    HIP_TRY(icp_grid_run(c.a, c.va, c.temp, c.temp_bytes, ctx->stream));
-    IcpReadback rb{};
-    rc = icp_pass(ctx, c, pose16, rb, nullptr);
-    if (rc != OUSTER_HIP_OK) return rc;
-    if (out->nn) HIP_TRY(hipMemcpyAsync(out->nn, c.a.nn, (size_t)c.a.n_src * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    if (out->r) HIP_TRY(hipMemcpyAsync(out->r, c.a.r, (size_t)c.a.n_src * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const bool solved = rb.pass.count >= ICP_MIN_POINTS;
-    out->count = rb.pass.count;
-    out->median = rb.pass.median, out->huber_delta = rb.pass.huber_delta;
-    for (int k = 0; k < OUSTER_HIP_ICP_SUMS; ++k) out->sums[k] = solved ? rb.pass.sums[k] : 0.0;
-    for (int k = 0; k < 3; ++k) {
-        out->centroid_x[k] = solved && c.method == ICP_POINT ? rb.pass.centroid_x[k] : 0.0;
-        out->centroid_q[k] = solved && c.method == ICP_POINT ? rb.pass.centroid_q[k] : 0.0;
-    }
-    bool stop = true;
-    icp_finish_pass(c.method, rb.pass.count, rb.pass.sums, rb.pass.centroid_x, rb.pass.centroid_q, pose16, out->next_pose, &stop);
-    out->stop = stop, out->solved = solved;
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_icp_align_host(ouster_hip_ctx* ctx, ouster_hip_icp_desc* desc) {
-    int rc = icp_validate_call(desc);
-    if (rc < 0) return rc;
-    if (rc == 1) return icp_guess_is_the_answer(desc), OUSTER_HIP_OK;
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t es = desc->dtype == OUSTER_HIP_F32 ? 4 : 8;
-    auto bytes = [es](uint64_t n, uint64_t stride) { return ((size_t)(n - 1) * (stride ? stride : 3) + 3) * es; };
-    std::vector<const void*> in = {desc->source_points, desc->target_points};
-    std::vector<size_t> in_bytes = {bytes(desc->n_source, desc->source_stride), bytes(desc->n_target, desc->target_stride)};
-    if (desc->source_normals) {
-        in.push_back(desc->source_normals), in_bytes.push_back(bytes(desc->n_source, desc->source_normal_stride));
-        in.push_back(desc->target_normals), in_bytes.push_back(bytes(desc->n_target, desc->target_normal_stride));
-    }
-    HostPlanes hin;
-    rc = hin.stage(ctx, in.data(), in_bytes.data(), (uint32_t)in.size(), 0, true);
-    if (rc != OUSTER_HIP_OK) return rc;
-    ouster_hip_icp_desc d = *desc;
-    d.source_points = hin.dev[0], d.target_points = hin.dev[1];
-    if (desc->source_normals) d.source_normals = hin.dev[2], d.target_normals = hin.dev[3];
-    rc = icp_device(ctx, &d);
-    if (rc != OUSTER_HIP_OK) return rc;
-    memcpy(desc->pose, d.pose, sizeof d.pose);
-    desc->iterations = d.iterations, desc->solved = d.solved, desc->correspondences = d.correspondences;
     return OUSTER_HIP_OK;
 }
 

@@ -1,5 +1,5 @@
 // pose_host.h -- the host half of interp_pose (csrc/host/pose_util.cpp): validation with the reference's messages and the
-// per-segment table.  Plain C++, no HIP: the C ABI (ouster_hip_capi.hip) calls it before anything touches the GPU.
+// per-segment table.  Plain C++, no HIP: the C ABI (capi_pose.hip) calls it before anything touches the GPU.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

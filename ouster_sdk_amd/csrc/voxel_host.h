@@ -1,6 +1,6 @@
 // voxel_host.h -- the host half of voxel down-sampling (csrc/host/voxel_util.cpp): validation with the reference's messages, the
 // choice of the GPU's reduction form, and the plain C++ restatement behind ouster_hip_voxel_downsample_ref.  Plain C++, no HIP:
-// the C ABI (ouster_hip_capi.hip) calls it before anything touches the GPU.
+// the C ABI (capi_voxel.hip) calls it before anything touches the GPU.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -1,0 +1,31 @@
+"""CPU-only: the workspace carver (ouster_sdk_amd/csrc/carve.h) that lays out the voxel and ICP workspaces.
+
+tests/cpp/test_carve.cpp -- g++ only, no HIP header or library -- measures and assigns mixed layouts (zero-size pieces, pieces
+of 1, 255, 256 and 257 bytes, a piece of 2^31 + 1 bytes that is counted and never touched) and checks that every piece is
+256-byte aligned, that pieces do not overlap, that the last one ends within the total, and that the measuring and the
+assigning pass agree on the total.  tests/cpp/Makefile also builds it with the address and undefined-behaviour sanitizers
+(_build/test_carve_san); this wrapper runs the plain build."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TOOL = os.path.join(ROOT, "tests", "cpp", "_build", "test_carve")
+
+
+def _tool():
+    """tests/cpp/_build/test_carve.  build() makes it; a tests/ directory put in place after the build has none, and makes it
+    here by the same rule of tests/cpp/Makefile (g++ only)."""
+    if not os.path.exists(TOOL):
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s", "_build/test_carve"])
+    assert os.path.exists(TOOL), "tests/cpp/_build/test_carve is missing: build() makes it"
+    return TOOL
+
+
+def test_carve_layouts():
+    r = subprocess.run([_tool()], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "carve: ok" in r.stdout, r.stdout + r.stderr
+
+
+def test_carve_test_links_no_hip_library():
+    out = subprocess.run(["ldd", _tool()], capture_output=True, text=True).stdout.lower()
+    assert "libc" in out and "hip" not in out and "hsa" not in out, out
