@@ -1,5 +1,5 @@
 // frame_ops_batch_tool.cpp -- drives the frame_ops members of hip::DeviceFrameBatch for tests/test_gpu_frame_ops_batch.py (built
-// by it with the flags of this directory's Makefile).
+// by this directory's Makefile).
 //   frame_ops_batch_tool <packets.bin> <h> <w> <n_frames> <masks.bin> <out_prefix> <clip_lo> <clip_hi> <key_lo> <key_hi>
 //                        <gate_min_m> <gate_max_m> <z_lo> <z_hi>
 //       packets.bin: [n_frames][w / 16][lidar_packet_size] bytes of RNG15_RFL8_NIR8_DUAL packets; masks.bin: u8 [2][h][w].
@@ -20,44 +20,11 @@
 #include <string>
 #include <vector>
 
-#include "ouster/core/lidar_scan.h"
-#include "ouster/hip/device_batch.h"
+#include "batch_fixture.h"
 
-using namespace ouster::sdk::core;
-namespace oh = ouster::sdk::hip;
+using namespace fixture;
 
-static SensorInfo make_info(uint32_t h, uint32_t w, int variant) {
-    SensorInfo info;
-    info.format.pixels_per_column = h;
-    info.format.columns_per_frame = w;
-    info.format.columns_per_packet = 16;
-    info.format.column_window = {0, static_cast<int>(w) - 1};
-    info.format.udp_profile_lidar = UDPProfileLidar::RNG15_RFL8_NIR8_DUAL;
-    for (uint32_t i = 0; i < h; ++i) {
-        const double az = (double[]){4.2, 1.4, -1.4, -4.2}[i % 4];
-        info.format.pixel_shift_by_row.push_back(static_cast<int>(std::nearbyint(az / 360.0 * w)) + (i == 1 ? static_cast<int>(w) : 0) -
-                                                 (i == 2 ? 2 * static_cast<int>(w) : 0));
-        info.beam_azimuth_angles.push_back(az);
-        info.beam_altitude_angles.push_back((h > 1 ? 21.0 - 42.0 * i / (h - 1.0) : 0.0) + 0.7 * variant);
-    }
-    info.prod_line = "OS-2-128";
-    info.beam_to_lidar_transform = default_beam_to_lidar_transform(info.prod_line);
-    info.lidar_to_sensor_transform = DEFAULT_LIDAR_TO_SENSOR;
-    info.sensor_to_body = mat4d::Identity();
-    info.fw_rev = "v3.2.0";
-    return info;
-}
-
-static bool refuses(const std::function<void()>& f) {
-    try {
-        f();
-    } catch (const std::invalid_argument&) {
-        return true;
-    } catch (const std::exception& e) {
-        std::printf("wrong exception: %s\n", e.what());
-    }
-    return false;
-}
+static bool refuses(const std::function<void()>& f) { return throws<std::invalid_argument>(f); }
 
 int main(int argc, char** argv) {
     if (argc != 15) {
@@ -69,7 +36,8 @@ int main(int argc, char** argv) {
         const std::string out = argv[6];
         const double clip_lo = std::atof(argv[7]), clip_hi = std::atof(argv[8]), key_lo = std::atof(argv[9]), key_hi = std::atof(argv[10]);
         const double gate_min = std::atof(argv[11]), gate_max = std::atof(argv[12]), z_lo = std::atof(argv[13]), z_hi = std::atof(argv[14]);
-        const std::vector<SensorInfo> sensors = {make_info(h, w, 0), make_info(h, w, 1)};
+        // rows 1 and 2 carry their shifts wrapped by +w and -2w
+        const std::vector<SensorInfo> sensors = {make_info(h, w, 0, true), make_info(h, w, 1, true)};
         oh::BatchOptions opt;
         opt.destagger = {"RANGE", "REFLECTIVITY"};
         opt.xyz = true;
@@ -77,19 +45,8 @@ int main(int argc, char** argv) {
         opt.gate_min_range = gate_min;
         opt.gate_max_range = gate_max;
         opt.auto_placement = false;
-        oh::DeviceFrameBatch b(sensors, n, opt);
-        {
-            std::ifstream f(argv[1], std::ios::binary);
-            const size_t ps = b.lidar_packet_size(), ppf = w / 16;
-            std::vector<uint8_t> pk(ps * ppf);
-            for (uint32_t fr = 0; fr < n; ++fr) {
-                f.read(reinterpret_cast<char*>(pk.data()), static_cast<std::streamsize>(pk.size()));
-                if (!f) throw std::runtime_error("packets file too short");
-                std::vector<const uint8_t*> ptrs;
-                for (size_t p = 0; p < ppf; ++p) ptrs.push_back(pk.data() + p * ps);
-                b.upload_frame_packets(fr, ptrs);
-            }
-        }
+        const auto batch = load_batch(sensors, n, opt, argv[1]);   // every packet, decoded
+        oh::DeviceFrameBatch& b = *batch;
         const size_t npx = static_cast<size_t>(h) * w;
         std::vector<uint8_t> masks(2 * npx);
         {
@@ -124,7 +81,6 @@ int main(int argc, char** argv) {
                 put(b.plane_bytes_per_frame(name), [&](uint32_t fr, void* d) { b.download_plane(name, fr, d, true); });
             for (int k = 0; k < 2; ++k) put(b.xyz_bytes_per_frame(), [&](uint32_t fr, void* d) { b.download_xyz(k, fr, d); });
         };
-        b.decode();
         dump();
         b.clip({"RANGE"}, clip_lo, clip_hi);
         dump();
@@ -158,13 +114,8 @@ int main(int argc, char** argv) {
         const uint64_t total = b.dewarp(gate_min, gate_max);
         std::vector<double> pts(total * 3);
         b.download_dewarped(pts.data(), nullptr, nullptr, nullptr);
-        {
-            std::ofstream f(out + ".dw", std::ios::binary);
-            f.write(reinterpret_cast<const char*>(pts.data()), static_cast<std::streamsize>(pts.size() * 8));
-            std::ofstream g(out + ".dwoff", std::ios::binary);
-            g.write(reinterpret_cast<const char*>(b.dewarped_frame_offsets().data()),
-                    static_cast<std::streamsize>(b.dewarped_frame_offsets().size() * 8));
-        }
+        write_file(out + ".dw", pts.data(), pts.size() * 8);
+        write_file(out + ".dwoff", b.dewarped_frame_offsets().data(), b.dewarped_frame_offsets().size() * 8);
         std::printf("dewarped %llu\n", static_cast<unsigned long long>(total));
 
         const std::vector<std::string> rng = {"RANGE"}, refl = {"REFLECTIVITY"};

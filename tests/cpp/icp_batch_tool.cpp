@@ -1,5 +1,5 @@
-// icp_batch_tool.cpp -- drives hip::DeviceFrameBatch::align_voxels for tests/test_gpu_icp_batch.py (built by it with the flags of this
-// directory's Makefile).
+// icp_batch_tool.cpp -- drives hip::DeviceFrameBatch::align_voxels for tests/test_gpu_icp_batch.py (built by this directory's
+// Makefile).
 //   icp_batch_tool <capture.pcap> <metadata.json> <n_frames> <voxel_size> <max_corr_dist> <out_prefix>
 // Two sensors with the capture's metadata (the second mounted elsewhere on the body), a batch of n_frames double-precision frames
 // filled with the capture's frames in turn.  Prints "pre_voxel_throws 1" when align_voxels before any voxel call is
@@ -21,17 +21,10 @@
 #include <string>
 #include <vector>
 
-#include "ouster/core/lidar_scan.h"
-#include "ouster/hip/device_batch.h"
+#include "batch_fixture.h"
 #include "ouster/pcap/pcap.h"
 
-using namespace ouster::sdk::core;
-namespace oh = ouster::sdk::hip;
-
-static void write_file(const std::string& path, const void* p, size_t bytes) {
-    std::ofstream f(path, std::ios::binary);
-    f.write(static_cast<const char*>(p), static_cast<std::streamsize>(bytes));
-}
+using namespace fixture;
 
 struct DeviceCopy {
     double* p = nullptr;
@@ -87,13 +80,7 @@ int main(int argc, char** argv) {
         b.decode();
 
         DeviceCopy nothing(std::vector<double>(60 * 3, 0.0));
-        bool pre = false;
-        try {
-            b.align_voxels(nothing.p, nullptr, 60, nullptr);
-        } catch (const std::invalid_argument&) {
-        } catch (const std::runtime_error&) {
-            pre = true;
-        }
+        const bool pre = throws<std::runtime_error>([&] { b.align_voxels(nothing.p, nullptr, 60, nullptr); });
         std::printf("pre_voxel_throws %d\n", pre ? 1 : 0);
 
         // the move: a rotation of 0.01 rad about (1, 2, 3) / sqrt(14) by Rodrigues' formula, and a few centimetres

@@ -1,5 +1,5 @@
 // image_batch_tool.cpp -- drives hip::DeviceFrameBatch::render_images for tests/test_gpu_image_processing.py and
-// tools/ab/image_bench.py (built by them with the flags of this directory's Makefile).
+// tools/ab/image_bench.py (built by this directory's Makefile).
 //   image_batch_tool render <packets.bin> <h> <w> <n_frames> <n_sensors> <out_prefix>
 //       packets.bin: [n_frames][w / 16][lidar_packet_size] bytes of RNG15_RFL8_NIR8_DUAL packets.  Decodes with NEAR_IR
 //       destaggered, render_images("NEAR_IR") TWICE (update_state true, then false) and writes
@@ -19,37 +19,9 @@
 #include <string>
 #include <vector>
 
-#include "ouster/core/lidar_scan.h"
-#include "ouster/hip/device_batch.h"
+#include "batch_fixture.h"
 
-using namespace ouster::sdk::core;
-namespace oh = ouster::sdk::hip;
-
-static SensorInfo make_info(uint32_t h, uint32_t w) {
-    SensorInfo info;
-    info.format.pixels_per_column = h;
-    info.format.columns_per_frame = w;
-    info.format.columns_per_packet = 16;
-    info.format.column_window = {0, static_cast<int>(w) - 1};
-    info.format.udp_profile_lidar = UDPProfileLidar::RNG15_RFL8_NIR8_DUAL;
-    for (uint32_t i = 0; i < h; ++i) {
-        const double az = (double[]){4.2, 1.4, -1.4, -4.2}[i % 4];
-        info.format.pixel_shift_by_row.push_back(static_cast<int>(std::nearbyint(az / 360.0 * w)));
-        info.beam_azimuth_angles.push_back(az);
-        info.beam_altitude_angles.push_back(h > 1 ? 21.0 - 42.0 * i / (h - 1.0) : 0.0);
-    }
-    info.prod_line = "OS-2-128";
-    info.beam_to_lidar_transform = default_beam_to_lidar_transform(info.prod_line);
-    info.lidar_to_sensor_transform = DEFAULT_LIDAR_TO_SENSOR;
-    info.sensor_to_body = mat4d::Identity();
-    info.fw_rev = "v3.2.0";
-    return info;
-}
-
-static void dump(const std::string& path, const void* p, size_t bytes) {
-    std::ofstream f(path, std::ios::binary);
-    f.write(static_cast<const char*>(p), static_cast<std::streamsize>(bytes));
-}
+using namespace fixture;
 
 int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
@@ -57,33 +29,22 @@ int main(int argc, char** argv) {
         if (mode == "render" && argc == 8) {
             const uint32_t h = std::atoi(argv[3]), w = std::atoi(argv[4]), n = std::atoi(argv[5]), ns = std::atoi(argv[6]);
             const std::string out = argv[7];
-            const SensorInfo info = make_info(h, w);
             oh::BatchOptions opt;
             opt.destagger = {"NEAR_IR"};
             opt.auto_placement = false;
-            oh::DeviceFrameBatch b(std::vector<SensorInfo>(ns, info), n, opt);
-            std::ifstream f(argv[2], std::ios::binary);
-            const size_t ps = b.lidar_packet_size(), ppf = w / 16;
-            std::vector<uint8_t> pk(ps * ppf);
-            for (uint32_t fr = 0; fr < n; ++fr) {
-                f.read(reinterpret_cast<char*>(pk.data()), static_cast<std::streamsize>(pk.size()));
-                if (!f) throw std::runtime_error("packets file too short");
-                std::vector<const uint8_t*> ptrs;
-                for (size_t p = 0; p < ppf; ++p) ptrs.push_back(pk.data() + p * ps);
-                b.upload_frame_packets(fr, ptrs);
-            }
-            b.decode();
+            const auto batch = load_batch(std::vector<SensorInfo>(ns, make_info(h, w, 0)), n, opt, argv[2]);
+            oh::DeviceFrameBatch& b = *batch;
             b.sync();
             const size_t pb = b.plane_bytes_per_frame("NEAR_IR"), npx = static_cast<size_t>(h) * w;
             std::vector<uint8_t> planes(pb * n);
             for (uint32_t fr = 0; fr < n; ++fr) b.download_plane("NEAR_IR", fr, planes.data() + pb * fr, true);
-            dump(out + ".planes", planes.data(), planes.size());
+            write_file(out + ".planes", planes.data(), planes.size());
             oh::ImagePipeline pipe(ns);
             std::vector<float> img(npx * n);
             for (int pass = 0; pass < 2; ++pass) {
                 b.render_images("NEAR_IR", pipe, pass == 0);
                 for (uint32_t fr = 0; fr < n; ++fr) b.download_image("NEAR_IR", fr, img.data() + npx * fr);
-                dump(out + (pass ? ".images1" : ".images0"), img.data(), img.size() * 4);
+                write_file(out + (pass ? ".images1" : ".images0"), img.data(), img.size() * 4);
             }
             std::vector<double> st;
             for (uint32_t s = 0; s < ns; ++s) {
@@ -92,12 +53,12 @@ int main(int argc, char** argv) {
                 const auto& d = pipe.beam_uniformity[s].dark_count();
                 st.insert(st.end(), d.begin(), d.end());
             }
-            dump(out + ".state", st.data(), st.size() * 8);
+            write_file(out + ".state", st.data(), st.size() * 8);
             std::printf("elem %zu\n", pb / npx);
             return 0;
         }
         if (mode == "refuse" && argc == 4) {
-            const SensorInfo info = make_info(std::atoi(argv[2]), std::atoi(argv[3]));
+            const SensorInfo info = make_info(std::atoi(argv[2]), std::atoi(argv[3]), 0);
             oh::BatchOptions opt;
             opt.destagger = {"RANGE"};
             opt.auto_placement = false;
@@ -115,7 +76,7 @@ int main(int argc, char** argv) {
         if (mode == "time" && argc == 4) {
             const uint32_t n = std::atoi(argv[2]);
             const int reps = std::atoi(argv[3]);
-            const SensorInfo info = make_info(128, 2048);
+            const SensorInfo info = make_info(128, 2048, 0);
             auto pf = std::make_shared<PacketFormat>(info);
             oh::BatchOptions opt;
             opt.destagger = {"NEAR_IR"};

@@ -1,5 +1,5 @@
 // normals_batch_tool.cpp -- drives normals / normals_device / download_normals of hip::DeviceFrameBatch for
-// tests/test_gpu_normals_batch.py (built by it with the flags of this directory's Makefile).
+// tests/test_gpu_normals_batch.py (built by this directory's Makefile).
 //   normals_batch_tool <packets.bin> <h> <w> <n_frames> <skip_frame> <skip_packet> <known.bin> <k> <out_prefix> <lo> <hi>
 //       packets.bin, known.bin: as for pose_batch_tool.cpp.  The two sensors of that tool, each with a sensor_to_body of its own
 //       (<prefix>.s2b, f64 [2][16]; <prefix>.shifts, i32 [h], the first sensor's).  Three dual-return batches, <B> =
@@ -27,37 +27,9 @@
 #include <string>
 #include <vector>
 
-#include "ouster/core/lidar_scan.h"
-#include "ouster/hip/device_batch.h"
+#include "batch_fixture.h"
 
-using namespace ouster::sdk::core;
-namespace oh = ouster::sdk::hip;
-
-static SensorInfo make_info(uint32_t h, uint32_t w, int variant) {
-    SensorInfo info;
-    info.format.pixels_per_column = h;
-    info.format.columns_per_frame = w;
-    info.format.columns_per_packet = 16;
-    info.format.column_window = {0, static_cast<int>(w) - 1};
-    info.format.udp_profile_lidar = UDPProfileLidar::RNG15_RFL8_NIR8_DUAL;
-    for (uint32_t i = 0; i < h; ++i) {
-        const double az = (double[]){4.2, 1.4, -1.4, -4.2}[i % 4];
-        info.format.pixel_shift_by_row.push_back(static_cast<int>(std::nearbyint(az / 360.0 * w)));
-        info.beam_azimuth_angles.push_back(az);
-        info.beam_altitude_angles.push_back((h > 1 ? 21.0 - 42.0 * i / (h - 1.0) : 0.0) + 0.7 * variant);
-    }
-    info.prod_line = "OS-2-128";
-    info.beam_to_lidar_transform = default_beam_to_lidar_transform(info.prod_line);
-    info.lidar_to_sensor_transform = DEFAULT_LIDAR_TO_SENSOR;
-    // a mount of its own per sensor: a turn about z and an offset
-    const double a = 0.3 + 0.4 * variant;
-    info.sensor_to_body = mat4d::Identity();
-    info.sensor_to_body.m[0] = std::cos(a), info.sensor_to_body.m[1] = -std::sin(a);
-    info.sensor_to_body.m[4] = std::sin(a), info.sensor_to_body.m[5] = std::cos(a);
-    info.sensor_to_body.m[3] = 0.35 - 0.6 * variant, info.sensor_to_body.m[7] = -0.2 + 0.15 * variant, info.sensor_to_body.m[11] = 1.1 + 0.25 * variant;
-    info.fw_rev = "v3.2.0";
-    return info;
-}
+using namespace fixture;
 
 int main(int argc, char** argv) {
     if (argc != 12) {
@@ -69,39 +41,19 @@ int main(int argc, char** argv) {
         const uint32_t skip_frame = std::atoi(argv[5]), skip_packet = std::atoi(argv[6]), k = std::atoi(argv[8]);
         const std::string prefix = argv[9];
         const double lo = std::atof(argv[10]), hi = std::atof(argv[11]);
-        std::vector<double> x_known(k);
-        std::vector<mat4d> poses_known(k);
-        {
-            std::ifstream f(argv[7], std::ios::binary);
-            f.read(reinterpret_cast<char*>(x_known.data()), static_cast<std::streamsize>(k * 8));
-            f.read(reinterpret_cast<char*>(poses_known.data()), static_cast<std::streamsize>(k * 128));
-            if (!f) throw std::runtime_error("known poses file too short");
-        }
-        const std::vector<SensorInfo> sensors = {make_info(h, w, 0), make_info(h, w, 1)};
+        std::vector<double> x_known;
+        std::vector<mat4d> poses_known;
+        read_known(argv[7], k, x_known, poses_known);
+        // a mount of its own per sensor
+        const std::vector<SensorInfo> sensors = {make_info(h, w, 0, false, true), make_info(h, w, 1, false, true)};
         {
             std::ofstream f(prefix + ".s2b", std::ios::binary);
             for (const auto& s : sensors) f.write(reinterpret_cast<const char*>(s.sensor_to_body.m), 128);
-            std::ofstream g(prefix + ".shifts", std::ios::binary);
             const std::vector<int32_t> sh(sensors[0].format.pixel_shift_by_row.begin(), sensors[0].format.pixel_shift_by_row.end());
-            g.write(reinterpret_cast<const char*>(sh.data()), static_cast<std::streamsize>(sh.size() * 4));
+            write_file(prefix + ".shifts", sh.data(), sh.size() * 4);
         }
         const size_t npx = static_cast<size_t>(h) * w;
-        auto make = [&](const oh::BatchOptions& opt) {
-            auto b = std::make_unique<oh::DeviceFrameBatch>(sensors, n, opt);
-            std::ifstream f(argv[1], std::ios::binary);
-            const size_t ps = b->lidar_packet_size(), ppf = w / 16;
-            std::vector<uint8_t> pk(ps * ppf);
-            for (uint32_t fr = 0; fr < n; ++fr) {
-                f.read(reinterpret_cast<char*>(pk.data()), static_cast<std::streamsize>(pk.size()));
-                if (!f) throw std::runtime_error("packets file too short");
-                std::vector<const uint8_t*> ptrs;
-                for (size_t p = 0; p < ppf; ++p)
-                    if (fr != skip_frame || p != skip_packet) ptrs.push_back(pk.data() + p * ps);
-                b->upload_frame_packets(fr, ptrs);
-            }
-            b->decode();
-            return b;
-        };
+        auto make = [&](const oh::BatchOptions& opt) { return load_batch(sensors, n, opt, argv[1], skip_frame, skip_packet); };
         bool all = true;
         struct Kind {
             const char* tag;
@@ -118,33 +70,18 @@ int main(int argc, char** argv) {
             if (kind.world) {
                 b->interp_poses(x_known, poses_known);
                 b->decode();   // a world-frame batch applies its poses inside decode()
-                std::vector<double> p(static_cast<size_t>(w) * 16);
-                std::ofstream f(base + "poses", std::ios::binary);
-                for (uint32_t fr = 0; fr < n; ++fr) {
-                    b->download_poses(fr, p.data());
-                    f.write(reinterpret_cast<const char*>(p.data()), static_cast<std::streamsize>(p.size() * 8));
-                }
+                write_frames(base + "poses", n, static_cast<size_t>(w) * 128, [&](uint32_t fr, double* p) { b->download_poses(fr, p); });
             }
             auto dump_inputs = [&](const std::string& pre) {
-                std::vector<uint8_t> buf(std::max(b->xyz_bytes_per_frame(), npx * 4));
                 for (int r = 0; r < 2; ++r) {
-                    std::ofstream fx(base + pre + "xyz" + std::to_string(r), std::ios::binary);
-                    std::ofstream fr_(base + pre + "r" + std::to_string(r), std::ios::binary);
-                    for (uint32_t fr = 0; fr < n; ++fr) {
-                        b->download_xyz(r, fr, buf.data());
-                        fx.write(reinterpret_cast<const char*>(buf.data()), static_cast<std::streamsize>(b->xyz_bytes_per_frame()));
-                        b->download_plane(r ? ChanField::RANGE2 : ChanField::RANGE, fr, buf.data());
-                        fr_.write(reinterpret_cast<const char*>(buf.data()), static_cast<std::streamsize>(npx * 4));
-                    }
+                    write_frames(base + pre + "xyz" + std::to_string(r), n, b->xyz_bytes_per_frame(),
+                                 [&](uint32_t fr, void* d) { b->download_xyz(r, fr, d); });
+                    write_frames(base + pre + "r" + std::to_string(r), n, npx * 4,
+                                 [&](uint32_t fr, void* d) { b->download_plane(r ? ChanField::RANGE2 : ChanField::RANGE, fr, d); });
                 }
             };
             auto dump_normals = [&](int r, const std::string& name) {
-                std::vector<double> nb(npx * 3);
-                std::ofstream f(base + name, std::ios::binary);
-                for (uint32_t fr = 0; fr < n; ++fr) {
-                    b->download_normals(r, fr, nb.data());
-                    f.write(reinterpret_cast<const char*>(nb.data()), static_cast<std::streamsize>(nb.size() * 8));
-                }
+                write_frames(base + name, n, npx * 24, [&](uint32_t fr, double* d) { b->download_normals(r, fr, d); });
             };
             dump_inputs("");
             bool ptr_ok = b->normals_device(0) == nullptr && b->normals_device(1) == nullptr;
@@ -182,25 +119,20 @@ int main(int argc, char** argv) {
                 dump_normals(1, "fd1");
             }
         }
-        auto throws = [&](const oh::BatchOptions& opt, bool dual) {
+        auto refuses = [&](const oh::BatchOptions& opt, bool dual) {
             auto b = make(opt);
             oh::NormalsOptions o;
             o.dual_return = dual;
-            try {
-                b->normals(o);
-            } catch (const std::invalid_argument&) {
-                return true;
-            }
-            return false;
+            return throws<std::invalid_argument>([&] { b->normals(o); });
         };
         oh::BatchOptions plain;
         plain.auto_placement = false;
-        const bool no_xyz = throws(plain, false);
+        const bool no_xyz = refuses(plain, false);
         oh::BatchOptions first_only;
         first_only.auto_placement = false;
         first_only.xyz = true;
         first_only.planes = {ChanField::RANGE};
-        const bool no_range2 = throws(first_only, true) && !throws(first_only, false);
+        const bool no_range2 = refuses(first_only, true) && !refuses(first_only, false);
         std::printf("no_xyz_throws %d\nno_range2_throws %d\n", no_xyz ? 1 : 0, no_range2 ? 1 : 0);
         return all && no_xyz && no_range2 ? 0 : 1;
     } catch (const std::exception& e) {

@@ -1,5 +1,5 @@
 // pose_batch_tool.cpp -- drives interp_poses / download_poses / poses_device of hip::DeviceFrameBatch for
-// tests/test_gpu_pose_batch.py (built by it with the flags of this directory's Makefile).
+// tests/test_gpu_pose_batch.py (built by this directory's Makefile).
 //   pose_batch_tool <packets.bin> <h> <w> <n_frames> <skip_frame> <skip_packet> <known.bin> <k> <out_prefix> <min_range> <max_range>
 //       packets.bin: [n_frames][w / 16][lidar_packet_size] bytes of RNG15_RFL8_NIR8_DUAL packets; packet <skip_packet> of frame
 //       <skip_frame> is left out.  known.bin: k doubles (seconds), then k x 16 doubles.  The two sensors of
@@ -25,32 +25,9 @@
 #include <string>
 #include <vector>
 
-#include "ouster/core/lidar_scan.h"
-#include "ouster/hip/device_batch.h"
+#include "batch_fixture.h"
 
-using namespace ouster::sdk::core;
-namespace oh = ouster::sdk::hip;
-
-static SensorInfo make_info(uint32_t h, uint32_t w, int variant) {
-    SensorInfo info;
-    info.format.pixels_per_column = h;
-    info.format.columns_per_frame = w;
-    info.format.columns_per_packet = 16;
-    info.format.column_window = {0, static_cast<int>(w) - 1};
-    info.format.udp_profile_lidar = UDPProfileLidar::RNG15_RFL8_NIR8_DUAL;
-    for (uint32_t i = 0; i < h; ++i) {
-        const double az = (double[]){4.2, 1.4, -1.4, -4.2}[i % 4];
-        info.format.pixel_shift_by_row.push_back(static_cast<int>(std::nearbyint(az / 360.0 * w)));
-        info.beam_azimuth_angles.push_back(az);
-        info.beam_altitude_angles.push_back((h > 1 ? 21.0 - 42.0 * i / (h - 1.0) : 0.0) + 0.7 * variant);
-    }
-    info.prod_line = "OS-2-128";
-    info.beam_to_lidar_transform = default_beam_to_lidar_transform(info.prod_line);
-    info.lidar_to_sensor_transform = DEFAULT_LIDAR_TO_SENSOR;
-    info.sensor_to_body = mat4d::Identity();
-    info.fw_rev = "v3.2.0";
-    return info;
-}
+using namespace fixture;
 
 struct Dewarped {
     std::vector<uint8_t> pts;
@@ -81,14 +58,9 @@ int main(int argc, char** argv) {
         const uint32_t skip_frame = std::atoi(argv[5]), skip_packet = std::atoi(argv[6]), k = std::atoi(argv[8]);
         const std::string prefix = argv[9];
         const double lo = std::atof(argv[10]), hi = std::atof(argv[11]);
-        std::vector<double> x_known(k);
-        std::vector<mat4d> poses_known(k);
-        {
-            std::ifstream f(argv[7], std::ios::binary);
-            f.read(reinterpret_cast<char*>(x_known.data()), static_cast<std::streamsize>(k * 8));
-            f.read(reinterpret_cast<char*>(poses_known.data()), static_cast<std::streamsize>(k * 128));
-            if (!f) throw std::runtime_error("known poses file too short");
-        }
+        std::vector<double> x_known;
+        std::vector<mat4d> poses_known;
+        read_known(argv[7], k, x_known, poses_known);
         const std::vector<SensorInfo> sensors = {make_info(h, w, 0), make_info(h, w, 1)};
         bool all = true;
         for (const bool f64 : {false, true}) {
@@ -97,29 +69,9 @@ int main(int argc, char** argv) {
             opt.xyz = true;
             opt.xyz_f64 = f64;
             opt.auto_placement = false;
-            auto make = [&]() {
-                auto b = std::make_unique<oh::DeviceFrameBatch>(sensors, n, opt);
-                std::ifstream f(argv[1], std::ios::binary);
-                const size_t ps = b->lidar_packet_size(), ppf = w / 16;
-                std::vector<uint8_t> pk(ps * ppf);
-                for (uint32_t fr = 0; fr < n; ++fr) {
-                    f.read(reinterpret_cast<char*>(pk.data()), static_cast<std::streamsize>(pk.size()));
-                    if (!f) throw std::runtime_error("packets file too short");
-                    std::vector<const uint8_t*> ptrs;
-                    for (size_t p = 0; p < ppf; ++p)
-                        if (fr != skip_frame || p != skip_packet) ptrs.push_back(pk.data() + p * ps);
-                    b->upload_frame_packets(fr, ptrs);
-                }
-                b->decode();
-                return b;
-            };
+            auto make = [&]() { return load_batch(sensors, n, opt, argv[1], skip_frame, skip_packet); };
             auto dump_poses = [&](oh::DeviceFrameBatch& b, const std::string& name) {
-                std::vector<double> p(static_cast<size_t>(w) * 16);
-                std::ofstream f(prefix + "." + tag + "." + name, std::ios::binary);
-                for (uint32_t fr = 0; fr < n; ++fr) {
-                    b.download_poses(fr, p.data());
-                    f.write(reinterpret_cast<const char*>(p.data()), static_cast<std::streamsize>(p.size() * 8));
-                }
+                write_frames(prefix + "." + tag + "." + name, n, static_cast<size_t>(w) * 128, [&](uint32_t fr, double* p) { b.download_poses(fr, p); });
             };
             auto b1 = make();
             {
@@ -169,8 +121,7 @@ int main(int argc, char** argv) {
                 b2->sync();
                 if (hipMemcpy(rows.data(), b2->pose_rows_device(), rows.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
                     throw std::runtime_error("hipMemcpy(pose rows) failed");
-                std::ofstream f(prefix + ".f32.rows2", std::ios::binary);
-                f.write(reinterpret_cast<const char*>(rows.data()), static_cast<std::streamsize>(rows.size() * 4));
+                write_file(prefix + ".f32.rows2", rows.data(), rows.size() * 4);
             }
         }
         return all ? 0 : 1;

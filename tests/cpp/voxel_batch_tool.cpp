@@ -1,5 +1,5 @@
 // voxel_batch_tool.cpp -- drives voxel_downsample / voxel_downsample_with_normals / voxels_device / download_voxels of
-// hip::DeviceFrameBatch for tests/test_gpu_voxel_batch.py (built by it with the flags of this directory's Makefile).
+// hip::DeviceFrameBatch for tests/test_gpu_voxel_batch.py (built by this directory's Makefile).
 //   voxel_batch_tool <packets.bin> <h> <w> <n_frames> <skip_frame> <skip_packet> <known.bin> <k> <out_prefix> <lo> <hi> <vs_a> <vs_b>
 //       packets.bin, known.bin: as for normals_batch_tool.cpp, with its two sensors.  Two dual-return body-frame batches,
 //       <B> = b64 (xyz_f64) and b32 (float); each gets interp_poses(known) and leaves
@@ -26,52 +26,9 @@
 #include <string>
 #include <vector>
 
-#include "ouster/core/lidar_scan.h"
-#include "ouster/hip/device_batch.h"
+#include "batch_fixture.h"
 
-using namespace ouster::sdk::core;
-namespace oh = ouster::sdk::hip;
-
-static SensorInfo make_info(uint32_t h, uint32_t w, int variant) {
-    SensorInfo info;
-    info.format.pixels_per_column = h;
-    info.format.columns_per_frame = w;
-    info.format.columns_per_packet = 16;
-    info.format.column_window = {0, static_cast<int>(w) - 1};
-    info.format.udp_profile_lidar = UDPProfileLidar::RNG15_RFL8_NIR8_DUAL;
-    for (uint32_t i = 0; i < h; ++i) {
-        const double az = (double[]){4.2, 1.4, -1.4, -4.2}[i % 4];
-        info.format.pixel_shift_by_row.push_back(static_cast<int>(std::nearbyint(az / 360.0 * w)));
-        info.beam_azimuth_angles.push_back(az);
-        info.beam_altitude_angles.push_back((h > 1 ? 21.0 - 42.0 * i / (h - 1.0) : 0.0) + 0.7 * variant);
-    }
-    info.prod_line = "OS-2-128";
-    info.beam_to_lidar_transform = default_beam_to_lidar_transform(info.prod_line);
-    info.lidar_to_sensor_transform = DEFAULT_LIDAR_TO_SENSOR;
-    const double a = 0.3 + 0.4 * variant;
-    info.sensor_to_body = mat4d::Identity();
-    info.sensor_to_body.m[0] = std::cos(a), info.sensor_to_body.m[1] = -std::sin(a);
-    info.sensor_to_body.m[4] = std::sin(a), info.sensor_to_body.m[5] = std::cos(a);
-    info.sensor_to_body.m[3] = 0.35 - 0.6 * variant, info.sensor_to_body.m[7] = -0.2 + 0.15 * variant, info.sensor_to_body.m[11] = 1.1 + 0.25 * variant;
-    info.fw_rev = "v3.2.0";
-    return info;
-}
-
-static void write_file(const std::string& path, const void* p, size_t bytes) {
-    std::ofstream f(path, std::ios::binary);
-    f.write(static_cast<const char*>(p), static_cast<std::streamsize>(bytes));
-}
-
-template <class E, class F>
-static bool throws(F f) {
-    try {
-        f();
-    } catch (const E&) {
-        return true;
-    } catch (const std::exception&) {
-    }
-    return false;
-}
+using namespace fixture;
 
 int main(int argc, char** argv) {
     if (argc != 14) {
@@ -83,39 +40,18 @@ int main(int argc, char** argv) {
         const uint32_t skip_frame = std::atoi(argv[5]), skip_packet = std::atoi(argv[6]), k = std::atoi(argv[8]);
         const std::string prefix = argv[9];
         const double lo = std::atof(argv[10]), hi = std::atof(argv[11]), vs_a = std::atof(argv[12]), vs_b = std::atof(argv[13]);
-        std::vector<double> x_known(k);
-        std::vector<mat4d> poses_known(k);
-        {
-            std::ifstream f(argv[7], std::ios::binary);
-            f.read(reinterpret_cast<char*>(x_known.data()), static_cast<std::streamsize>(k * 8));
-            f.read(reinterpret_cast<char*>(poses_known.data()), static_cast<std::streamsize>(k * 128));
-            if (!f) throw std::runtime_error("known poses file too short");
-        }
-        const std::vector<SensorInfo> sensors = {make_info(h, w, 0), make_info(h, w, 1)};
+        std::vector<double> x_known;
+        std::vector<mat4d> poses_known;
+        read_known(argv[7], k, x_known, poses_known);
+        const std::vector<SensorInfo> sensors = {make_info(h, w, 0, false, true), make_info(h, w, 1, false, true)};
         const size_t npx = static_cast<size_t>(h) * w;
-        auto make = [&](const oh::BatchOptions& opt) {
-            auto b = std::make_unique<oh::DeviceFrameBatch>(sensors, n, opt);
-            std::ifstream f(argv[1], std::ios::binary);
-            const size_t ps = b->lidar_packet_size(), ppf = w / 16;
-            std::vector<uint8_t> pk(ps * ppf);
-            for (uint32_t fr = 0; fr < n; ++fr) {
-                f.read(reinterpret_cast<char*>(pk.data()), static_cast<std::streamsize>(pk.size()));
-                if (!f) throw std::runtime_error("packets file too short");
-                std::vector<const uint8_t*> ptrs;
-                for (size_t p = 0; p < ppf; ++p)
-                    if (fr != skip_frame || p != skip_packet) ptrs.push_back(pk.data() + p * ps);
-                b->upload_frame_packets(fr, ptrs);
-            }
-            b->decode();
-            return b;
-        };
         bool all = true;
         for (const bool f64 : {true, false}) {
             oh::BatchOptions opt;
             opt.xyz = true;
             opt.xyz_f64 = f64;
             opt.auto_placement = false;
-            auto b = make(opt);
+            auto b = load_batch(sensors, n, opt, argv[1], skip_frame, skip_packet);
             const std::string tag = f64 ? "b64" : "b32", base = prefix + "." + tag + ".";
             const size_t es = f64 ? 8 : 4;
             b->interp_poses(x_known, poses_known);
@@ -165,15 +101,8 @@ int main(int argc, char** argv) {
                 oh::NormalsOptions no;
                 no.staggered_output = true;
                 b->normals(no);
-                std::vector<uint8_t> xyz(b->xyz_bytes_per_frame());
-                std::vector<double> nrm(npx * 3);
-                std::ofstream fx(base + pre + "xyz0", std::ios::binary), fn(base + pre + "nrm0", std::ios::binary);
-                for (uint32_t fr = 0; fr < n; ++fr) {
-                    b->download_xyz(0, fr, xyz.data());
-                    fx.write(reinterpret_cast<const char*>(xyz.data()), static_cast<std::streamsize>(xyz.size()));
-                    b->download_normals(0, fr, nrm.data());
-                    fn.write(reinterpret_cast<const char*>(nrm.data()), static_cast<std::streamsize>(nrm.size() * 8));
-                }
+                write_frames(base + pre + "xyz0", n, b->xyz_bytes_per_frame(), [&](uint32_t fr, void* d) { b->download_xyz(0, fr, d); });
+                write_frames(base + pre + "nrm0", n, npx * 24, [&](uint32_t fr, double* d) { b->download_normals(0, fr, d); });
                 voxels(pre + "wnp", b->voxel_downsample_with_normals(vs_b), true, pre + "wnn");
             };
             round("", true);

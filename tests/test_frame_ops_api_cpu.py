@@ -4,12 +4,12 @@ C++, compiled and linked against include/ouster/core/frame_ops.h), the metadata 
 loud failure of pixel work without a GPU."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import cpp_tools
 import frame_ops_model as M
 from conftest import ROOT, has_gpu
 from ouster_sdk_amd import _capi as capi
@@ -164,21 +164,8 @@ def test_pixel_work_without_a_gpu_raises_and_leaves_the_frame():
 
 
 def test_cpp_caller_compiles_links_and_runs():
-    """The flags of tests/cpp/Makefile (the build of the other C++ tests), on tests/cpp/frame_ops_snippet.cpp: every validation
-    error through C++, the metadata functions, and the pixel work (or its refusal without a GPU)."""
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "frame_ops_snippet")
-    lib = os.path.join(ROOT, "ouster_sdk_amd", "lib")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "frame_ops_snippet.cpp"),
-                           "-L" + lib, "-louster_core_amd", "-louster_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
-                           "-Wl,-rpath," + lib, "-Wl,-rpath," + os.path.join(rocm, "lib")])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    p = subprocess.run([exe, META], capture_output=True, text=True, env=env, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    """tests/cpp/frame_ops_snippet.cpp, built by tests/cpp/Makefile with the flags of the other C++ tests and -Werror: every
+    validation error through C++, the metadata functions, and the pixel work (or its refusal without a GPU)."""
+    p = cpp_tools.run("frame_ops_snippet", [META], timeout=300)
     assert "meta 128 OS-0-128 -> 32 OS-0-32" in p.stdout, p.stdout
     assert p.stdout.splitlines()[-1].startswith("ok" if has_gpu() else "no-gpu"), p.stdout

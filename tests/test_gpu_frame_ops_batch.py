@@ -9,14 +9,13 @@ The batch destaggers every frame with the first sensor's pixel_shift_by_row (dec
 their shifts.  Guard bands around device planes are checked on the C ABI level (tests/test_gpu_frame_ops.py): a batch owns
 its allocations and exposes nothing around them."""
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_tools
 import frame_ops_model as M
-from conftest import ROOT, has_gpu
+from conftest import has_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -24,23 +23,8 @@ H, W, N = 32, 512, 5
 SECOND = M.SECOND_RETURN_FIELDS
 
 
-def build_tool():
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    out = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out, exist_ok=True)
-    exe, lib = os.path.join(out, "frame_ops_batch_tool"), os.path.join(ROOT, "ouster_sdk_amd", "lib")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(rocm, "include"), "-D__HIP_PLATFORM_AMD__", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "frame_ops_batch_tool.cpp"), "-L" + lib, "-louster_core_amd",
-                           "-louster_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + lib,
-                           "-Wl,-rpath," + os.path.join(rocm, "lib")])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    return exe, env
-
-
 def tool_shifts(h, w):
-    """make_info of the tool"""
+    """make_info(h, w, variant, wrap_shifts = true) of tests/cpp/batch_fixture.h"""
     out = []
     for i in range(h):
         az = [4.2, 1.4, -1.4, -4.2][i % 4]
@@ -75,17 +59,15 @@ def run(oracle, tmp_path_factory):
     nz = r[r > 0]
     p = dict(clip_lo=float(np.percentile(nz, 15)), clip_hi=float(np.percentile(nz, 85)), key_lo=40.0, key_hi=90.0,
              gate_min=float(np.percentile(nz, 5)) / 1000.0, gate_max=float(np.percentile(nz, 95)) / 1000.0)
-    exe, env = build_tool()
     # a band around z = 0 sized from the data: about a third of the live points by r * sin(altitude) (the tool's beam angles),
     # plus the points earlier ops have already put at the origin
     alt = np.deg2rad(21.0 - 42.0 * np.arange(H) / (H - 1.0))
     z = np.abs(r.astype(np.float64) * 1e-3 * np.sin(alt)[None, :, None])
     band = float(np.percentile(z[r > 0], 30))
     p["z_lo"], p["z_hi"] = -band, band
-    args = [exe, str(tmp / "packets.bin"), str(H), str(W), str(N), str(tmp / "masks.bin"), str(tmp / "o")] + \
+    args = [tmp / "packets.bin", H, W, N, tmp / "masks.bin", tmp / "o"] + \
            [repr(p[k]) for k in ("clip_lo", "clip_hi", "key_lo", "key_hi", "gate_min", "gate_max", "z_lo", "z_hi")]
-    res = subprocess.run(args, capture_output=True, text=True, env=env, timeout=600)
-    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+    res = cpp_tools.run("frame_ops_batch_tool", args)
     layout = [(ln.split()[1], int(ln.split()[2])) for ln in res.stdout.splitlines() if ln.startswith("plane ")]
     dt = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
 

@@ -6,14 +6,14 @@ tests/icp_model.py: 8 x the difference between the model with left-fold sums and
 (floor 8 * 2^-52 * max(1, |t|)), measured from the model alone.  align_voxels before any voxel call is std::runtime_error."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_tools
 import icp_cases as K
 import icp_model as M
-from conftest import PCAPS, ROOT, has_gpu
+from conftest import PCAPS, has_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -22,29 +22,12 @@ VOXEL = 1.5
 DIST = 0.5
 
 
-def build_tool():
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    out = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out, exist_ok=True)
-    exe, lib = os.path.join(out, "icp_batch_tool"), os.path.join(ROOT, "ouster_sdk_amd", "lib")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(rocm, "include"), "-D__HIP_PLATFORM_AMD__", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "icp_batch_tool.cpp"), "-L" + lib, "-louster_core_amd",
-                           "-louster_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + lib,
-                           "-Wl,-rpath," + os.path.join(rocm, "lib")])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    return exe, env
-
-
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     assert has_gpu()
     tmp = tmp_path_factory.mktemp("icp_batch")
-    exe, env = build_tool()
-    res = subprocess.run([exe, os.path.join(PCAPS, "OS-1-128_v2.3.0_1024x10_lb_n3.pcap"), os.path.join(PCAPS, "OS-1-128_v2.3.0_1024x10.json"),
-                          str(N_FRAMES), str(VOXEL), str(DIST), str(tmp / "o")], capture_output=True, text=True, env=env, timeout=300)
-    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+    res = cpp_tools.run("icp_batch_tool", [os.path.join(PCAPS, "OS-1-128_v2.3.0_1024x10_lb_n3.pcap"), os.path.join(PCAPS, "OS-1-128_v2.3.0_1024x10.json"),
+                                           N_FRAMES, VOXEL, DIST, tmp / "o"], timeout=300)
     out = {"stdout": res.stdout}
     for route in ("plane", "point"):
         b = {}

@@ -273,17 +273,10 @@ def test_update_batch_equals_single_updates(gpu, dtype):
         assert same_bits(np.ascontiguousarray(alone[i]), b), i
 
 
-def _batch_tool():
-    """tests/cpp/image_batch_tool.cpp, built with the flags of tests/cpp/Makefile"""
-    from image_tool import build_tool
-    return build_tool()
-
-
-def _run(args, env):
-    import subprocess
-    p = subprocess.run(args, capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
-    return p.stdout
+def _run(args):
+    """tests/cpp/image_batch_tool.cpp, built by tests/cpp/Makefile -> what it printed"""
+    import cpp_tools
+    return cpp_tools.run("image_batch_tool", args).stdout
 
 
 def test_render_images_two_sensors_equals_model_per_sensor(gpu, oracle, tmp_path):
@@ -297,8 +290,7 @@ def test_render_images_two_sensors_equals_model_per_sensor(gpu, oracle, tmp_path
     packets, _ = O.synth_packets(cal, n)
     src = tmp_path / "packets.bin"
     np.ascontiguousarray(packets).tofile(src)
-    exe, env = _batch_tool()
-    out = _run([exe, "render", str(src), str(h), str(w), str(n), str(S), str(tmp_path / "r")], env)
+    out = _run(["render", src, h, w, n, S, tmp_path / "r"])
     elem = int(out.split("elem")[1].split()[0])
     planes = np.fromfile(tmp_path / "r.planes", {1: np.uint8, 2: np.uint16, 4: np.uint32}[elem]).reshape(n, h, w)
     want_planes = []
@@ -324,12 +316,10 @@ def test_render_images_two_sensors_equals_model_per_sensor(gpu, oracle, tmp_path
 
 
 def test_render_images_on_a_plane_that_was_not_requested_throws(gpu):
-    exe, env = _batch_tool()
-    assert _run([exe, "refuse", "32", "512"], env).startswith("invalid_argument")
+    assert _run(["refuse", "32", "512"]).startswith("invalid_argument")
 
 
 def test_cpp_update_on_a_std_vector_equals_pool_memory(gpu):
     """The C++ classes themselves, ten calls: a std::vector-backed ImgRef (foreign memory, staged) gives the bits and the state
     of the same calls on an img_t (pool memory, in place)."""
-    exe, env = _batch_tool()
-    assert _run([exe, "cpp_update"], env).strip() == "same"
+    assert _run(["cpp_update"]).strip() == "same"

@@ -6,50 +6,15 @@ staggered one (normal i belongs to point i), for the single-return form, and aga
 smooth scene (a slanted wall with a step, a second return some hundred mm behind it), so that the model takes its cases B and C
 and not only the lone-pixel case A; the model's classification is asserted.  A batch without XYZ, and the dual form on a batch
 without RANGE2, throw std::invalid_argument."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import cpp_tools
 import normals_model as M
-from conftest import ROOT, has_gpu
-from test_gpu_pose_batch import trajectory
+from batch_cases import FILTER_HI, FILTER_LO, H, K, N, SKIP_FRAME, SKIP_PACKET, W, scene, write_known, write_packets
+from conftest import has_gpu
 
 pytestmark = pytest.mark.gpu
-
-H, W, N, K = 8, 128, 5, 9
-SKIP_FRAME, SKIP_PACKET = 3, 2
-T0_NS = 1_700_000_123_000_000_000
-FRAME_NS, COL_NS = 100_000_000, 100_000_000 // W
-FILTER_LO, FILTER_HI = 3000.0, 3600.0   # mm: filter_field invalidates the ranges INSIDE
-
-
-def build_tool():
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    out = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out, exist_ok=True)
-    exe, lib = os.path.join(out, "normals_batch_tool"), os.path.join(ROOT, "ouster_sdk_amd", "lib")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(rocm, "include"), "-D__HIP_PLATFORM_AMD__", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "normals_batch_tool.cpp"), "-L" + lib, "-louster_core_amd",
-                           "-louster_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + lib,
-                           "-Wl,-rpath," + os.path.join(rocm, "lib")])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    return exe, env
-
-
-def scene(f, keep):
-    """RANGE / RANGE2 of frame f, (H, W) mm in multiples of 8 (the profile's range unit): a wall whose distance varies smoothly
-    with row and column and steps by 1.2 m at a quarter of the columns, the second return 296 - 744 mm behind the first (both
-    sides of the 500 mm thin-object rule); zero where `keep` is false"""
-    u, v = np.mgrid[0:H, 0:W]
-    r1 = 2500.0 + 900.0 * np.sin(2 * np.pi * (v + 7 * f) / W) + 60.0 * u + np.where((v + 5 * f) % W < W // 4, 1200.0, 0.0)
-    r2 = r1 + 296.0 + 64.0 * ((u + v + f) % 8)
-    r1 = (r1.astype(np.int64) // 8 * 8).astype(np.uint32)
-    r2 = (r2.astype(np.int64) // 8 * 8).astype(np.uint32)
-    return np.where(keep, r1, 0).astype(np.uint32), np.where(keep, r2, 0).astype(np.uint32)
 
 
 def destagger(a, shifts):
@@ -63,29 +28,10 @@ def destagger(a, shifts):
 @pytest.fixture(scope="module")
 def run(oracle, tmp_path_factory):
     assert has_gpu()
-    O = oracle
     tmp = tmp_path_factory.mktemp("normals_batch")
-    cal = O.synthetic_calib(h=H, w=W, profile="RNG15_RFL8_NIR8_DUAL")
-    pf = cal.packet_format()
-    packets = []
-    for f in range(N):
-        fr = O.Frame.for_profile(cal.profile, cal.h, cal.w, cal.cpp, with_window=cal.with_window)
-        O.randomize_frame(fr, pf, 4000 + f, 0.1, frame_id=700 + f)
-        r1, r2 = scene(f, fr.plane("RANGE") != 0)   # a tenth of the pixels stays without range
-        fr.plane("RANGE")[:] = r1
-        fr.plane("RANGE2")[:] = r2
-        fr.timestamp[:] = T0_NS + f * FRAME_NS + np.arange(W, dtype=np.uint64) * np.uint64(COL_NS)
-        pk, _ = O.frame_to_packets(fr, pf, cal.init_id & 0xFFFFFF, cal.prod_sn)
-        packets.append(pk)
-    np.ascontiguousarray(np.stack(packets)).tofile(tmp / "packets.bin")
-    xk, poses = trajectory()
-    with open(tmp / "known.bin", "wb") as fh:
-        fh.write(xk.tobytes())
-        fh.write(poses.tobytes())
-    exe, env = build_tool()
-    res = subprocess.run([exe, str(tmp / "packets.bin"), str(H), str(W), str(N), str(SKIP_FRAME), str(SKIP_PACKET), str(tmp / "known.bin"),
-                          str(K), str(tmp / "o"), str(FILTER_LO), str(FILTER_HI)], capture_output=True, text=True, env=env, timeout=600)
-    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+    write_packets(oracle, tmp, scene)
+    write_known(tmp)
+    res = cpp_tools.run("normals_batch_tool", [tmp / "packets.bin", H, W, N, SKIP_FRAME, SKIP_PACKET, tmp / "known.bin", K, tmp / "o", FILTER_LO, FILTER_HI])
     out = {"stdout": res.stdout, "s2b": np.fromfile(tmp / "o.s2b", np.float64).reshape(2, 16),
            "shifts": np.fromfile(tmp / "o.shifts", np.int32)}
     assert out["shifts"].shape == (H,) and (out["shifts"] > 0).any() and (out["shifts"] < 0).any()

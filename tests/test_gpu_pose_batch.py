@@ -6,84 +6,24 @@ unit); the missing packet's columns keep their bits -- identity on a fresh batch
 dewarp() after interp_poses equals dewarp() of a batch that got the same poses through download_poses -> upload_poses, for a
 float batch (which reads the float rows written by the same launch) and for an xyz_f64 batch.  The C ABI's column form is
 checked on its own for the float rows and the untouched bytes."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import cpp_tools
 import pose_model as M
-from conftest import ROOT, has_gpu
+from batch_cases import COL_NS, FRAME_NS, H, K, N, SKIP_FRAME, SKIP_PACKET, T0_NS, W, write_known, write_packets
+from conftest import has_gpu
 
 pytestmark = pytest.mark.gpu
-
-H, W, N, K = 8, 128, 5, 9
-SKIP_FRAME, SKIP_PACKET = 3, 2
-T0_NS = 1_700_000_123_000_000_000
-FRAME_NS, COL_NS = 100_000_000, 100_000_000 // W
-
-
-def build_tool():
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    out = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out, exist_ok=True)
-    exe, lib = os.path.join(out, "pose_batch_tool"), os.path.join(ROOT, "ouster_sdk_amd", "lib")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(rocm, "include"), "-D__HIP_PLATFORM_AMD__", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "pose_batch_tool.cpp"), "-L" + lib, "-louster_core_amd",
-                           "-louster_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + lib,
-                           "-Wl,-rpath," + os.path.join(rocm, "lib")])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    return exe, env
-
-
-def rodrigues(axis, angle):
-    axis = np.asarray(axis, dtype=np.float64) / np.linalg.norm(axis)
-    k = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-    return np.eye(3) + np.sin(angle) * k + (1 - np.cos(angle)) * (k @ k)
-
-
-def trajectory():
-    """9 poses 0.06 - 0.08 s apart, from just before the first column to just after the last: relative rotations of 0.05 - 0.4
-    rad, positions within 1e3 m (the conditions of the golden maker)"""
-    rng = np.random.default_rng(77)
-    span = (N - 1) * FRAME_NS + W * COL_NS
-    xk = T0_NS * 1e-9 - 0.01 + np.concatenate([[0.0], np.cumsum(rng.uniform(0.06, 0.08, K - 1))])
-    assert xk[-1] > (T0_NS + span) * 1e-9
-    rot, poses = rodrigues([0.2, -0.3, 1.0], 0.7), []
-    for i in range(K):
-        if i:
-            rot = rot @ rodrigues(rng.normal(size=3), rng.uniform(0.05, 0.4))
-        m = np.eye(4)
-        m[:3, :3], m[:3, 3] = rot, rng.uniform(-1e3, 1e3, 3)
-        poses.append(m.reshape(16))
-    return xk, np.array(poses)
 
 
 @pytest.fixture(scope="module")
 def run(oracle, tmp_path_factory):
     assert has_gpu()
-    O = oracle
     tmp = tmp_path_factory.mktemp("pose_batch")
-    cal = O.synthetic_calib(h=H, w=W, profile="RNG15_RFL8_NIR8_DUAL")
-    pf = cal.packet_format()
-    packets = []
-    for f in range(N):
-        fr = O.Frame.for_profile(cal.profile, cal.h, cal.w, cal.cpp, with_window=cal.with_window)
-        O.randomize_frame(fr, pf, 4000 + f, 0.1, frame_id=700 + f)
-        fr.timestamp[:] = T0_NS + f * FRAME_NS + np.arange(W, dtype=np.uint64) * np.uint64(COL_NS)
-        pk, _ = O.frame_to_packets(fr, pf, cal.init_id & 0xFFFFFF, cal.prod_sn)
-        packets.append(pk)
-    np.ascontiguousarray(np.stack(packets)).tofile(tmp / "packets.bin")
-    xk, poses = trajectory()
-    with open(tmp / "known.bin", "wb") as fh:
-        fh.write(xk.tobytes())
-        fh.write(poses.tobytes())
-    exe, env = build_tool()
-    res = subprocess.run([exe, str(tmp / "packets.bin"), str(H), str(W), str(N), str(SKIP_FRAME), str(SKIP_PACKET), str(tmp / "known.bin"),
-                          str(K), str(tmp / "o"), "1.0", "200.0"], capture_output=True, text=True, env=env, timeout=600)
-    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+    write_packets(oracle, tmp)
+    xk, poses = write_known(tmp)
+    res = cpp_tools.run("pose_batch_tool", [tmp / "packets.bin", H, W, N, SKIP_FRAME, SKIP_PACKET, tmp / "known.bin", K, tmp / "o", "1.0", "200.0"])
     out = {"stdout": res.stdout, "xk": xk, "poses": poses}
     for tag in ("f32", "f64"):
         raw = np.fromfile(tmp / ("o.%s.hdr" % tag), np.uint8)

@@ -5,68 +5,30 @@ normals(staggered_output) then voxel_downsample_with_normals must equal the mode
 -- bit for bit, row order included -- and both again after filter_field on RANGE and a fresh dewarp().  The three precondition
 errors (no dewarp() yet, no normals, normals in the destaggered layout) are std::invalid_argument, and a call that throws leaves no
 result behind."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import batch_cases as B
+import cpp_tools
 import voxel_cases as K
 import voxel_model as M
-from conftest import ROOT, has_gpu
-from test_gpu_normals_batch import COL_NS, FRAME_NS, H, N, SKIP_FRAME, SKIP_PACKET, T0_NS, W, scene
-from test_gpu_pose_batch import trajectory
+from batch_cases import FILTER_HI, FILTER_LO, H, N, SKIP_FRAME, SKIP_PACKET, W
+from conftest import has_gpu
 
 pytestmark = pytest.mark.gpu
 
-KNOWN = 9
-FILTER_LO, FILTER_HI = 3000.0, 3600.0   # mm: filter_field invalidates the ranges INSIDE
 VS_A, VS_B = 0.25, 1.0
 TAGS = (("b64", np.float64), ("b32", np.float32))
-
-
-def build_tool():
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    out = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out, exist_ok=True)
-    exe, lib = os.path.join(out, "voxel_batch_tool"), os.path.join(ROOT, "ouster_sdk_amd", "lib")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(rocm, "include"), "-D__HIP_PLATFORM_AMD__", "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "voxel_batch_tool.cpp"), "-L" + lib, "-louster_core_amd",
-                           "-louster_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + lib,
-                           "-Wl,-rpath," + os.path.join(rocm, "lib")])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    return exe, env
 
 
 @pytest.fixture(scope="module")
 def run(oracle, tmp_path_factory):
     assert has_gpu()
-    O = oracle
     tmp = tmp_path_factory.mktemp("voxel_batch")
-    cal = O.synthetic_calib(h=H, w=W, profile="RNG15_RFL8_NIR8_DUAL")
-    pf = cal.packet_format()
-    packets = []
-    for f in range(N):
-        fr = O.Frame.for_profile(cal.profile, cal.h, cal.w, cal.cpp, with_window=cal.with_window)
-        O.randomize_frame(fr, pf, 4000 + f, 0.1, frame_id=700 + f)
-        r1, r2 = scene(f, fr.plane("RANGE") != 0)   # a tenth of the pixels stays without range
-        fr.plane("RANGE")[:] = r1
-        fr.plane("RANGE2")[:] = r2
-        fr.timestamp[:] = T0_NS + f * FRAME_NS + np.arange(W, dtype=np.uint64) * np.uint64(COL_NS)
-        pk, _ = O.frame_to_packets(fr, pf, cal.init_id & 0xFFFFFF, cal.prod_sn)
-        packets.append(pk)
-    np.ascontiguousarray(np.stack(packets)).tofile(tmp / "packets.bin")
-    xk, poses = trajectory()
-    with open(tmp / "known.bin", "wb") as fh:
-        fh.write(xk.tobytes())
-        fh.write(poses.tobytes())
-    exe, env = build_tool()
-    res = subprocess.run([exe, str(tmp / "packets.bin"), str(H), str(W), str(N), str(SKIP_FRAME), str(SKIP_PACKET), str(tmp / "known.bin"),
-                          str(KNOWN), str(tmp / "o"), str(FILTER_LO), str(FILTER_HI), str(VS_A), str(VS_B)],
-                         capture_output=True, text=True, env=env, timeout=600)
-    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+    B.write_packets(oracle, tmp, B.scene)
+    B.write_known(tmp)
+    res = cpp_tools.run("voxel_batch_tool", [tmp / "packets.bin", H, W, N, SKIP_FRAME, SKIP_PACKET, tmp / "known.bin", B.K, tmp / "o",
+                                             FILTER_LO, FILTER_HI, VS_A, VS_B])
     out = {"stdout": res.stdout}
     for tag, ft in TAGS:
         b = {}

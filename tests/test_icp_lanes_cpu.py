@@ -5,28 +5,20 @@ elements behind both.  Keys, hash insert (real threads race for the slots), ids,
 library's source; the scan and the stable sort, rocPRIM's on the device, are plain C++ here.  The sum kernels (k_icp_sums_point_a /
 _b, k_icp_sums_plane), k_icp_median and k_icp_fold use cross-lane operations or device-only launches and are covered on the GPU only
 (tests/test_gpu_icp.py)."""
-import os
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_tools
 import icp_cases as K
 import icp_model as M
-from conftest import ROOT
 
 
 @pytest.fixture(scope="module")
 def lanes():
-    out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "icp_lanes")
-    cpp = os.path.join(ROOT, "tests", "cpp")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-std=c++20", "-ffp-contract=off", "-pthread",
-                           "-I" + os.path.join(cpp, "host_lanes"), "-I" + cpp, "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(cpp, "icp_lanes.cpp")])
-    return exe
+    return cpp_tools.build("icp_lanes")[0]
 
 
 def run(exe, tmp_path, arrays, pose, max_corr_dist, angle, table_log2=None):

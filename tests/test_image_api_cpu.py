@@ -2,12 +2,12 @@
 shapes, the TypeError on a wrong dtype, the loud failure without a GPU (no CPU fallback) and a C++ caller that compiles and
 links against include/ouster/core/image_processing.h."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import cpp_tools
 from conftest import ROOT, has_gpu
 from ouster_sdk_amd import _capi as capi
 
@@ -57,19 +57,6 @@ def test_update_without_a_gpu_raises_and_leaves_the_image(dtype):
 
 
 def test_cpp_caller_compiles_links_and_runs():
-    """The flags of tests/cpp/Makefile (the build of the other C++ tests), on tests/cpp/image_processing_snippet.cpp."""
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "image_processing_snippet")
-    lib = os.path.join(ROOT, "ouster_sdk_amd", "lib")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "tests", "cpp", "image_processing_snippet.cpp"),
-                           "-L" + lib, "-louster_core_amd", "-louster_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
-                           "-Wl,-rpath," + lib, "-Wl,-rpath," + os.path.join(rocm, "lib")])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    p = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    """tests/cpp/image_processing_snippet.cpp, built by tests/cpp/Makefile with the flags of the other C++ tests and -Werror"""
+    p = cpp_tools.run("image_processing_snippet", [], timeout=300)
     assert p.stdout.startswith("ok" if has_gpu() else "no-gpu"), p.stdout

@@ -3,29 +3,20 @@
 what can go wrong without a GPU in sight -- index arithmetic across frames, returns, tiles and staggered rows, the order of every
 floating-point operation, the hand-over of the per-frame constants -- on the small scenes of tests/test_gpu_normals.py; the
 device's own arithmetic and the C ABI around the kernels are that test's business."""
-import os
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_tools
 import normals_model as M
 import test_gpu_normals as G
-from conftest import ROOT
 
 
 @pytest.fixture(scope="module")
 def lanes():
-    out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "normals_lanes")
-    cpp = os.path.join(ROOT, "tests", "cpp")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-std=c++20", "-ffp-contract=off", "-pthread",
-                           "-I" + os.path.join(cpp, "host_lanes"), "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(cpp, "normals_lanes.cpp"),
-                           os.path.join(ROOT, "ouster_sdk_amd", "csrc", "host", "normals_util.cpp")])
-    return exe
+    return cpp_tools.build("normals_lanes")[0]
 
 
 def run(exe, tmp_path, xyz, r1, xyz2, r2, psr, f32=False, shifts=None, staggered_out=False, origins=None, poses=None, s2b=None):

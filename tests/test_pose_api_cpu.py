@@ -4,12 +4,12 @@ the C ABI, through Python and through C++ (tests/cpp/pose_snippet.cpp, compiled 
 include/ouster/core/pose_util.h), and the loud failure of the per-x work without a GPU."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import cpp_tools
 import pose_model as M
 from conftest import ROOT, has_gpu
 from ouster_sdk_amd import _capi as capi
@@ -136,19 +136,7 @@ def test_per_x_work_without_a_gpu_raises():
 
 
 def test_cpp_caller_compiles_links_and_runs():
-    """The flags of tests/cpp/Makefile (the build of the other C++ tests), with -Werror, on tests/cpp/pose_snippet.cpp"""
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "pose_snippet")
-    lib = os.path.join(ROOT, "ouster_sdk_amd", "lib")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tests", "cpp", "pose_snippet.cpp"),
-                           "-L" + lib, "-louster_core_amd", "-louster_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
-                           "-Wl,-rpath," + lib, "-Wl,-rpath," + os.path.join(rocm, "lib")])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    p = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    """tests/cpp/pose_snippet.cpp, built by tests/cpp/Makefile with the flags of the other C++ tests and -Werror"""
+    p = cpp_tools.run("pose_snippet", [], timeout=300)
     assert "validation ok" in p.stdout, p.stdout
     assert p.stdout.splitlines()[-1].startswith("ok" if has_gpu() else "no-gpu"), p.stdout

@@ -4,12 +4,12 @@ through Python and through C++ (tests/cpp/voxel_snippet.cpp, compiled and linked
 the GPU entry points without a GPU, and the two host-routed combinations, which work without one."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import cpp_tools
 import voxel_cases as K
 import voxel_model as M
 from conftest import ROOT, has_gpu
@@ -191,19 +191,7 @@ def test_python_face_names_defaults_and_errors():
 
 
 def test_cpp_caller_compiles_links_and_runs():
-    """The flags of tests/cpp/Makefile (the build of the other C++ tests), with -Werror, on tests/cpp/voxel_snippet.cpp"""
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "voxel_snippet")
-    lib = os.path.join(ROOT, "ouster_sdk_amd", "lib")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tests", "cpp", "voxel_snippet.cpp"),
-                           "-L" + lib, "-louster_core_amd", "-louster_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
-                           "-Wl,-rpath," + lib, "-Wl,-rpath," + os.path.join(rocm, "lib")])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    p = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    """tests/cpp/voxel_snippet.cpp, built by tests/cpp/Makefile with the flags of the other C++ tests and -Werror"""
+    p = cpp_tools.run("voxel_snippet", [], timeout=300)
     assert "validation ok" in p.stdout and "host route ok" in p.stdout, p.stdout
     assert p.stdout.splitlines()[-1].startswith("ok" if has_gpu() else "no-gpu"), p.stdout

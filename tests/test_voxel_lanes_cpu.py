@@ -5,30 +5,22 @@ reduce and write are the library's source; the scans and the stable sort, rocPRI
 what can go wrong without a GPU in sight -- the validity rules, the floor at negative coordinates, the order of every sum, strides,
 the compaction, what a refusal leaves behind; the device's own arithmetic and the C ABI around the kernels are
 tests/test_gpu_voxel.py's business."""
-import os
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_tools
 import voxel_cases as K
 import voxel_model as M
-from conftest import ROOT
 
 FORM_AVERAGE, FORM_FIRST, FORM_LAST, FORM_NORMALS = 0, 1, 2, 3
 
 
 @pytest.fixture(scope="module")
 def lanes():
-    out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "voxel_lanes")
-    cpp = os.path.join(ROOT, "tests", "cpp")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-std=c++20", "-ffp-contract=off", "-pthread",
-                           "-I" + os.path.join(cpp, "host_lanes"), "-I" + cpp, "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(cpp, "voxel_lanes.cpp")])
-    return exe
+    return cpp_tools.build("voxel_lanes")[0]
 
 
 def run(exe, tmp_path, frame, voxel_size, form, min_pts=1, normals=None, dtype=np.float64, stride=None, table_log2=None, capacity=None):

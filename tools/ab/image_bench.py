@@ -29,7 +29,7 @@ N, H, W, WARM, REPS, PASSES = 256, 128, 2048, 5, 20, 4
 
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from image_tool import build_tool  # noqa: E402  (tests/image_tool.py builds tests/cpp/image_batch_tool)
+import cpp_tools  # noqa: E402  (tests/cpp_tools.py builds tests/cpp/image_batch_tool)
 
 
 def main():
@@ -85,7 +85,7 @@ def main():
                          "model_bytes_per_frame": model[name], "frac_8TBps": round(model[name] * N / (t * 1e-3) / PEAK, 4)}
     res["percentiles"]["frac_lines"] = round(px * 2 * PASSES * N / (res["percentiles"]["ms"] * 1e-3) / PEAK, 4)
     assert int(n_pos.min()) > 100 and float(out.max()) <= 1.0 and float(out.min()) >= 0.0
-    exe, env = build_tool()
+    exe, env = cpp_tools.build("image_batch_tool")
     whole = subprocess.run([exe, "time", str(N), "20"], capture_output=True, text=True, env=env, timeout=600)
     res["render_images"] = json.loads(whole.stdout.strip().splitlines()[-1]) if whole.returncode == 0 else {"error": whole.stdout[-300:]}
     print(json.dumps({"what": "display images, NEAR_IR u16 -> f32, %d frames of %d x %d, median of %d after %d warm-ups" % (N, H, W, REPS, WARM),
