@@ -1,5 +1,5 @@
-// capi_internal.h -- what the translation units of the C ABI share: ouster_hip_capi.hip (context, formats, LUTs, decode, the
-// standalone calls) and one capi_<feature>.hip next to each feature's kernels.  Internal to libouster_hip.so, not installed.
+// capi_internal.h -- what the translation units of the C ABI share: ouster_hip_capi.hip (context, formats, decode) and one
+// capi_<feature>.hip next to each feature's kernels.  Internal to libouster_hip.so, not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +29,7 @@ int fail_msg(int code, const char* msg);
 
 // bytes of an F32 / F64 element; 0: `dtype` is neither
 inline size_t float_elem(int dtype) { return dtype == OUSTER_HIP_F32 ? 4 : dtype == OUSTER_HIP_F64 ? 8 : 0; }
+inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 struct DevBuf {
     void* p = nullptr;
@@ -137,7 +138,33 @@ struct ouster_hip_ctx {
     int last_tile_cols = 0, last_tile_rows = 0;  // tile of the last k_decode launch
 };
 
+struct ouster_hip_format {
+    ouster_hip_format_desc desc;
+    ouster_hip_dev::Geometry g;
+    int spec_id = ouster_hip_dev::SPEC_GENERIC;
+    int8_t spec_of_desc[OUSTER_HIP_MAX_FIELDS];
+    int spec_nf = 0, spec_r1 = -1, spec_r2 = -1;
+};
+
+struct ouster_hip_lut {
+    int device = 0;  // the tables outlive the context that uploaded them
+    uint32_t w = 0, h = 0;
+    bool separable = false;
+    ouster_hip_dev::LutDev dev{};
+    void *d_beam = nullptr, *d_col = nullptr, *d_dir = nullptr, *d_ofs = nullptr;
+    // host copy of the full double LUT for ouster_hip_lut_export
+    std::vector<double> direction, offset;
+};
+
 namespace ouster_hip_dev {
+
+// per-call device tables of the context (ouster_hip_capi.hip).  Both synchronise the stream when they upload and not otherwise.
+//   ensure_luts     `l` -> ctx->luts, unless it is there already; 0 or -1
+//   stage_offsets   the destination column offsets of `shifts` (destagger; inverse: stagger) -> ctx->offsets; *out is the device
+//                   array.  Voids ouster_hip_decode's cache key for ctx->offsets.  OUSTER_HIP_OK, or the code fail() returned.
+// (Hidden: the library's dynamic symbols stay what they were.)
+__attribute__((visibility("hidden"))) int ensure_luts(ouster_hip_ctx* c, const std::vector<LutDev>& l);
+__attribute__((visibility("hidden"))) int stage_offsets(ouster_hip_ctx* c, const int32_t* shifts, uint32_t h, uint32_t w, int inverse, const int32_t** out);
 
 // A small host table -> ctx->tables, safe by construction for back-to-back asynchronous calls: the source is copied into
 // page-locked staging owned by the context, the staging is reused only after the event behind its last copy has completed,

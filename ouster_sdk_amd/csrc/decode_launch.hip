@@ -10,6 +10,18 @@
 
 namespace ouster_hip_dev {
 
+// the decode's profile table: what ouster_hip_format_create matches a format description against (the Spec* tables of kernels_common.h)
+const FieldC* spec_fields(int spec_id, int* nf, uint32_t* chan, int* r1, int* r2) {
+    switch (spec_id) {
+        case SPEC_DUAL_LB: *nf = SpecDualLB::nf; *chan = SpecDualLB::chan; *r1 = 0; *r2 = 4; return SpecDualLB::f;
+        case SPEC_LB: *nf = SpecLB::nf; *chan = SpecLB::chan; *r1 = 0; *r2 = -1; return SpecLB::f;
+        case SPEC_SINGLE: *nf = SpecSingle::nf; *chan = SpecSingle::chan; *r1 = 0; *r2 = -1; return SpecSingle::f;
+        case SPEC_DUAL: *nf = SpecDual::nf; *chan = SpecDual::chan; *r1 = 0; *r2 = 3; return SpecDual::f;
+        case SPEC_LEGACY: *nf = SpecLegacy::nf; *chan = SpecLegacy::chan; *r1 = 0; *r2 = -1; return SpecLegacy::f;
+        default: *nf = 0; *chan = 0; *r1 = *r2 = -1; return nullptr;
+    }
+}
+
 #define OUSTER_DECL_SPEC(sfx)                                                                             \
     hipError_t launch_decode_##sfx(const DecodeArgs& a, int tile, int xyzm, int device, hipStream_t st); \
     hipError_t launch_decode_wide_##sfx(const DecodeArgs& a, int tw, int xyzm, int device, hipStream_t st, uint32_t resident);

@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void k_pose_interp(PoseInterpArgs a) {
     }
 }
 
-// rotation * p + translation in T, row by row: the expression of the dense dewarp (k_standalone.hip, k_dewarp), here without
+// rotation * p + translation in T, row by row: the expression of the dense dewarp (k_dewarp.hip, k_dewarp), here without
 // contraction, which is how the reference's host loop is compiled
 template <class T>
 __global__ __launch_bounds__(256) void k_pose_transform(PoseTransformArgs a) {

@@ -1,5 +1,5 @@
 // kernels_common.h -- device helpers shared by the kernel translation units
-// (k_decode.hip is compiled once per packet-profile specialisation, k_standalone.hip once).
+// (k_decode.hip is compiled once per packet-profile specialisation, the standalone k_<feature>.hip files once each).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -128,7 +128,7 @@ struct __attribute__((packed, aligned(1))) pk16 { uint32_t a, b, c, d; };
 #define OUSTER_NT_STORES 0   // experiment switch (tools/ab/nt_variants.sh): non-temporal hint on EVERY plane / xyz store
 #endif
 #ifndef OUSTER_NT_STANDALONE
-#define OUSTER_NT_STANDALONE 1   // the hint on the stores of the standalone kernels (k_standalone.hip): +1.9 ... +5.7 % in-process on cold inputs
+#define OUSTER_NT_STANDALONE 1   // the hint on the stores of the standalone kernels (k_destagger / k_cartesian / k_dewarp.hip): +1.9 ... +5.7 % in-process on cold inputs
 #endif
 #ifndef OUSTER_NT_U32
 #define OUSTER_NT_U32 0      // experiment switch: the hint on the 4-byte plane stores (and whatever else asks for it)

@@ -1,9 +1,8 @@
 // ouster_hip_capi.hip -- host side of the C ABI declared in include/ouster_hip.h.
-// Owns the context (stream, scratch), turns format / calibration descriptions into
-// device tables and launches the kernels of ouster_hip_kernels.hip.  No compute happens
-// on the host except the one-off XYZ table construction (make_xyz_lut is a one-off in the
-// reference too: ouster_core/src/xyzlut.cpp:11-89, cached per sensor in sensor_info.cpp:260-275).
-// The entry points of a feature (images, frame_ops, pose, normals, voxel, ICP) are in capi_<feature>.hip, next to its kernels.
+// Owns the error channel and the context (stream, scratch, knobs, tuning cache), turns format descriptions into the decode's
+// tables, and runs the fused decode: the variant tuner, the launch plan (decode_plan.cpp) and the launches of k_decode*.hip.
+// Every other entry point is in capi_<feature>.hip, next to the feature's kernels (destagger, cartesian and the LUTs, dewarp,
+// OSF, images, frame_ops, pose, normals, voxel, ICP).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -36,114 +35,6 @@ int fail_msg(int code, const char* msg) { return fail(code, "%s", msg); }
 static void tune_forget(ouster_hip_ctx* c) {   // the one place the tuner's events are destroyed
     for (auto& kv : c->tune) kv.second.destroy();
     c->tune.clear();
-}
-
-struct ouster_hip_format {
-    ouster_hip_format_desc desc;
-    Geometry g;
-    int spec_id = SPEC_GENERIC;
-    int8_t spec_of_desc[OUSTER_HIP_MAX_FIELDS];
-    int spec_nf = 0, spec_r1 = -1, spec_r2 = -1;
-};
-
-struct ouster_hip_lut {
-    int device = 0;  // the tables outlive the context that uploaded them
-    uint32_t w = 0, h = 0;
-    bool separable = false;
-    LutDev dev{};
-    void *d_beam = nullptr, *d_col = nullptr, *d_dir = nullptr, *d_ofs = nullptr;
-    // host copy of the full double LUT for ouster_hip_lut_export
-    std::vector<double> direction, offset;
-};
-
-// ---------------------------------------------------------------------------------------
-// host math: impl::make_xyz_lut (ouster_core/src/xyzlut.cpp:11-89), full LUT in double
-// ---------------------------------------------------------------------------------------
-static void host_full_lut(const ouster_hip_calib& c, std::vector<double>& direction,
-                          std::vector<double>& offset) {
-    const size_t w = c.w, h = c.h;
-    direction.assign(w * h * 3, 0.0);
-    offset.assign(w * h * 3, 0.0);
-    const double* b2l = c.beam_to_lidar_transform;
-    const double* tf = c.transform;
-    const double bx = b2l[3], bz = b2l[11];
-    double n = bx;
-    if (bz != 0) n = std::sqrt(std::pow(bx, 2) + std::pow(bz, 2));
-    const bool per_beam = (c.n_angles == h);
-    const double step = M_PI * 2.0 / static_cast<double>(w);
-    for (size_t row = 0; row < h; ++row) {
-        for (size_t col = 0; col < w; ++col) {
-            const size_t i = row * w + col;
-            double enc, azi, alt;
-            if (per_beam) {
-                enc = 2.0 * M_PI - static_cast<double>(col) * step;
-                azi = -c.azimuth_angles_deg[row] * M_PI / 180.0;
-                alt = c.altitude_angles_deg[row] * M_PI / 180.0;
-            } else {
-                enc = 0;
-                azi = c.azimuth_angles_deg[i] * M_PI / 180.0;
-                alt = c.altitude_angles_deg[i] * M_PI / 180.0;
-            }
-            const double d[3] = {std::cos(enc + azi) * std::cos(alt),
-                                 std::sin(enc + azi) * std::cos(alt), std::sin(alt)};
-            const double o[3] = {std::cos(enc) * bx - d[0] * n, std::sin(enc) * bx - d[1] * n,
-                                 -d[2] * n + bz};
-            for (int r = 0; r < 3; ++r) {
-                double dd = 0, oo = 0;
-                for (int k = 0; k < 3; ++k) {
-                    dd += d[k] * tf[r * 4 + k];
-                    oo += o[k] * tf[r * 4 + k];
-                }
-                oo += tf[r * 4 + 3];
-                direction[i * 3 + r] = dd * c.range_unit;
-                offset[i * 3 + r] = oo * c.range_unit;
-            }
-        }
-    }
-}
-
-// separable form of the same table: see the derivation in DESIGN.md ("XYZ tables")
-static void host_separable_tables(const ouster_hip_calib& c, std::vector<double>& beam,
-                                  std::vector<double>& col, double& n_out) {
-    const size_t w = c.w, h = c.h;
-    const double* b2l = c.beam_to_lidar_transform;
-    const double* tf = c.transform;
-    const double ru = c.range_unit;
-    const double bx = b2l[3], bz = b2l[11];
-    double n = bx;
-    if (bz != 0) n = std::sqrt(std::pow(bx, 2) + std::pow(bz, 2));
-    n_out = n;
-    auto rot = [&](const double v[3], double out[3]) {
-        for (int r = 0; r < 3; ++r)
-            out[r] = v[0] * tf[r * 4 + 0] + v[1] * tf[r * 4 + 1] + v[2] * tf[r * 4 + 2];
-    };
-    beam.assign(h * 9, 0.0);
-    for (size_t row = 0; row < h; ++row) {
-        const double azi = -c.azimuth_angles_deg[row] * M_PI / 180.0;
-        const double alt = c.altitude_angles_deg[row] * M_PI / 180.0;
-        const double A = std::cos(azi) * std::cos(alt), B = std::sin(azi) * std::cos(alt),
-                     Cc = std::sin(alt);
-        const double u[3] = {A, B, 0}, v[3] = {-B, A, 0}, wv[3] = {0, 0, Cc};
-        double ru_[3];
-        rot(u, ru_);
-        for (int k = 0; k < 3; ++k) beam[row * 9 + k] = ru_[k] * ru;
-        rot(v, ru_);
-        for (int k = 0; k < 3; ++k) beam[row * 9 + 3 + k] = ru_[k] * ru;
-        rot(wv, ru_);
-        for (int k = 0; k < 3; ++k) beam[row * 9 + 6 + k] = ru_[k] * ru;
-    }
-    col.assign(w * 5, 0.0);
-    const double step = M_PI * 2.0 / static_cast<double>(w);
-    for (size_t cc = 0; cc < w; ++cc) {
-        const double enc = 2.0 * M_PI - static_cast<double>(cc) * step;
-        const double cx = std::cos(enc), sx = std::sin(enc);
-        const double o[3] = {cx * bx, sx * bx, bz};
-        double ro[3];
-        rot(o, ro);
-        col[cc * 5 + 0] = cx;
-        col[cc * 5 + 1] = sx;
-        for (int k = 0; k < 3; ++k) col[cc * 5 + 2 + k] = (ro[k] + tf[k * 4 + 3]) * ru;
-    }
 }
 
 static void fill_geometry(const ouster_hip_format_desc& d, Geometry& g) {
@@ -386,106 +277,7 @@ int ouster_hip_format_create(ouster_hip_ctx* ctx, const ouster_hip_format_desc* 
 
 void ouster_hip_format_destroy(ouster_hip_format* f) { delete f; }
 
-// ---- lut -------------------------------------------------------------------------------
-static int upload(void** dptr, const void* src, size_t bytes, hipStream_t st) {
-    if (counted_malloc(dptr, bytes) != hipSuccess) return -1;
-    if (hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    return hipStreamSynchronize(st) == hipSuccess ? 0 : -1;
-}
-
-int ouster_hip_lut_create(ouster_hip_ctx* ctx, const ouster_hip_calib* c, ouster_hip_lut** out) {
-    if (!ctx || !c || !out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (c->w == 0 || c->h == 0)
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "lut dimensions must be greater than zero");
-    const size_t hw = (size_t)c->w * c->h;
-    if ((c->n_angles != c->h && c->n_angles != hw) || !c->azimuth_angles_deg ||
-        !c->altitude_angles_deg)
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "unexpected frame dimensions");
-    HIP_TRY(hipSetDevice(ctx->device));
-    ouster_hip_lut* L = new (std::nothrow) ouster_hip_lut();
-    if (!L) return fail(OUSTER_HIP_ERR_RUNTIME, "out of memory");
-    L->device = ctx->device;
-    L->w = c->w;
-    L->h = c->h;
-    host_full_lut(*c, L->direction, L->offset);
-    int rc = 0;
-    if (c->n_angles == c->h) {
-        std::vector<double> beam, col;
-        double n;
-        host_separable_tables(*c, beam, col, n);
-        L->separable = true;
-        rc |= upload(&L->d_beam, beam.data(), beam.size() * 8, ctx->stream);
-        rc |= upload(&L->d_col, col.data(), col.size() * 8, ctx->stream);
-        L->dev.beam_tab = (const double*)L->d_beam;
-        L->dev.col_tab = (const double*)L->d_col;
-        L->dev.n = n;
-        L->dev.full_dtype = 0;
-    } else {
-        rc |= upload(&L->d_dir, L->direction.data(), hw * 24, ctx->stream);
-        rc |= upload(&L->d_ofs, L->offset.data(), hw * 24, ctx->stream);
-        L->dev.full_dir = L->d_dir;
-        L->dev.full_ofs = L->d_ofs;
-        L->dev.full_dtype = OUSTER_HIP_F64;
-    }
-    if (rc) {
-        ouster_hip_lut_destroy(L);
-        return fail(OUSTER_HIP_ERR_RUNTIME, "LUT upload failed");
-    }
-    *out = L;
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_lut_create_from_arrays(ouster_hip_ctx* ctx, const void* direction,
-                                      const void* offset, uint32_t h, uint32_t w, int dtype,
-                                      ouster_hip_lut** out) {
-    if (!ctx || !direction || !offset || !out)
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (w == 0 || h == 0)
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "lut dimensions must be greater than zero");
-    if (!float_elem(dtype))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "LUT dtype must be F32 or F64");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t hw = (size_t)w * h, es = float_elem(dtype);
-    ouster_hip_lut* L = new (std::nothrow) ouster_hip_lut();
-    if (!L) return fail(OUSTER_HIP_ERR_RUNTIME, "out of memory");
-    L->device = ctx->device;
-    L->w = w;
-    L->h = h;
-    L->direction.resize(hw * 3);
-    L->offset.resize(hw * 3);
-    for (size_t i = 0; i < hw * 3; ++i) {
-        L->direction[i] = es == 4 ? (double)((const float*)direction)[i] : ((const double*)direction)[i];
-        L->offset[i] = es == 4 ? (double)((const float*)offset)[i] : ((const double*)offset)[i];
-    }
-    int rc = upload(&L->d_dir, direction, hw * 3 * es, ctx->stream);
-    rc |= upload(&L->d_ofs, offset, hw * 3 * es, ctx->stream);
-    if (rc) {
-        ouster_hip_lut_destroy(L);
-        return fail(OUSTER_HIP_ERR_RUNTIME, "LUT upload failed");
-    }
-    L->dev.full_dir = L->d_dir;
-    L->dev.full_ofs = L->d_ofs;
-    L->dev.full_dtype = dtype;
-    *out = L;
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_lut_export(const ouster_hip_lut* L, double* direction, double* offset) {
-    if (!L || !direction || !offset) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    memcpy(direction, L->direction.data(), L->direction.size() * 8);
-    memcpy(offset, L->offset.data(), L->offset.size() * 8);
-    return OUSTER_HIP_OK;
-}
-
-void ouster_hip_lut_destroy(ouster_hip_lut* L) {
-    if (!L) return;
-    (void)hipSetDevice(L->device);
-    counted_free((void*)L->d_beam);
-    counted_free((void*)L->d_col);
-    counted_free((void*)L->d_dir);
-    counted_free((void*)L->d_ofs);
-    delete L;
-}
+}  // extern "C"
 
 // ---- helpers for per-call device tables -------------------------------------------------
 // destination column offset per row with the reference's exact arithmetic:
@@ -514,7 +306,17 @@ static int ensure_offsets(ouster_hip_ctx* c, const std::vector<int32_t>& off) {
     return 0;
 }
 
-static int ensure_luts(ouster_hip_ctx* c, const std::vector<LutDev>& l) {
+// what the standalone destagger and the OSF stagger launch with (capi_internal.h)
+int ouster_hip_dev::stage_offsets(ouster_hip_ctx* c, const int32_t* shifts, uint32_t h, uint32_t w, int inverse, const int32_t** out) {
+    std::vector<int32_t> off;
+    dest_offsets(shifts, h, w, inverse, off);
+    if (ensure_offsets(c, off)) return fail(OUSTER_HIP_ERR_RUNTIME, "offset upload failed");
+    c->shifts_host.clear();  // ouster_hip_decode's cache key no longer describes `offsets`
+    *out = (const int32_t*)c->offsets.p;
+    return OUSTER_HIP_OK;
+}
+
+int ouster_hip_dev::ensure_luts(ouster_hip_ctx* c, const std::vector<LutDev>& l) {
     bool same = c->luts.p && l.size() == c->luts_host.size() &&
                 memcmp(l.data(), c->luts_host.data(), l.size() * sizeof(LutDev)) == 0;
     if (same) return 0;
@@ -527,7 +329,7 @@ static int ensure_luts(ouster_hip_ctx* c, const std::vector<LutDev>& l) {
     return 0;
 }
 
-static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+extern "C" {
 
 // ---- decode ------------------------------------------------------------------------------
 // packet_counts may live anywhere: device memory is used in place; host memory is copied with the
@@ -972,77 +774,6 @@ int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const u
     return OUSTER_HIP_OK;
 }
 
-// ---- standalone destagger -----------------------------------------------------------------
-int ouster_hip_destagger(ouster_hip_ctx* ctx, const void* src, void* dst, uint32_t h, uint32_t w,
-                         uint32_t elem_bytes, const int32_t* shifts, uint32_t n_shifts,
-                         int inverse, uint32_t n_images) {
-    if (!ctx || !shifts) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (n_shifts != h)
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "image height does not match shifts size");
-    if (n_images == 0 || h == 0 || w == 0) return OUSTER_HIP_OK;
-    if (!src || !dst || src == dst) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "bad image pointers");
-    if (elem_bytes == 0) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "elem_bytes is 0");
-    HIP_TRY(hipSetDevice(ctx->device));
-    std::vector<int32_t> off;
-    dest_offsets(shifts, h, w, inverse, off);
-    if (ensure_offsets(ctx, off)) return fail(OUSTER_HIP_ERR_RUNTIME, "offset upload failed");
-    ctx->shifts_host.clear();  // ouster_hip_decode's cache key no longer describes `offsets`
-    DestaggerArgs a{};
-    a.src = src;
-    a.dst = dst;
-    a.h = h;
-    a.w = w;
-    a.elem = elem_bytes;
-    a.offsets = (const int32_t*)ctx->offsets.p;
-    HIP_TRY(launch_destagger(a, n_images, ctx->stream));
-    return OUSTER_HIP_OK;
-}
-
-// ---- standalone cartesian -------------------------------------------------------------------
-int ouster_hip_cartesian(ouster_hip_ctx* ctx, const ouster_hip_lut* lut, const uint32_t* range,
-                         void* xyz, int xyz_dtype, uint32_t n_images) {
-    if (!ctx || !lut) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!float_elem(xyz_dtype))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "xyz_dtype must be F32 or F64");
-    if (n_images == 0) return OUSTER_HIP_OK;
-    if (!range || !xyz) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL image pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    CartesianArgs a{};
-    a.lut = lut->dev;
-    a.range = range;
-    a.xyz = xyz;
-    a.w = lut->w;
-    a.h = lut->h;
-    a.n_images = n_images;
-    a.xyz_dtype = xyz_dtype;
-    const size_t npx = (size_t)lut->w * lut->h;
-    a.vec_ok = al16(range) && al16(xyz) && (npx % 4 == 0);
-    const int mode = lut->separable ? (xyz_dtype == OUSTER_HIP_F32 ? 1 : 2) : 3;
-    HIP_TRY(launch_cartesian(a, mode, ctx->stream));
-    return OUSTER_HIP_OK;
-}
-
-// ---- dense dewarp -----------------------------------------------------------------------------
-int ouster_hip_dewarp(ouster_hip_ctx* ctx, const void* points, const double* poses, void* dewarped,
-                      int dtype, uint32_t h, uint32_t w, uint32_t n_images) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (!float_elem(dtype))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
-    if (n_images == 0 || h == 0 || w == 0) return OUSTER_HIP_OK;
-    if (!points || !poses || !dewarped) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    DewarpArgs a{};
-    a.points = points;
-    a.out = dewarped;
-    a.poses = poses;
-    a.w = w;
-    a.h = h;
-    a.n_images = n_images;
-    a.dtype = dtype;
-    HIP_TRY(launch_dewarp(a, ctx->stream));
-    return OUSTER_HIP_OK;
-}
-
 // ---- host containers (include/ouster_hip.h, "host containers") -----------------------------------
 int ouster_hip_device_alloc(ouster_hip_ctx* ctx, size_t bytes, void** out) {
     if (!ctx || !out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -1073,259 +804,6 @@ int ouster_hip_copy_in(ouster_hip_ctx* ctx, void* dev_dst, const void* host_src,
 int ouster_hip_copy_out(ouster_hip_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes) {
     if (!ctx || (bytes && (!host_dst || !dev_src))) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     if (bytes) HIP_TRY(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_destagger_host(ouster_hip_ctx* ctx, const void* src, void* dst, uint32_t h, uint32_t w,
-                              uint32_t elem_bytes, const int32_t* shifts, uint32_t n_shifts, int inverse) {
-    if (!ctx || !shifts) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (n_shifts != h) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "image height does not match shifts size");
-    if (h == 0 || w == 0) return OUSTER_HIP_OK;
-    if (!src || !dst || elem_bytes == 0) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "bad image arguments");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)h * w * elem_bytes;
-    Staging st(ctx);
-    // in place (src == dst) in the reference copies rows through each other: not a supported call there either; go through scratch
-    const auto in = st.input(src, bytes), out = st.output(dst, bytes, src == dst);
-    int rc = st.stage();
-    if (rc != OUSTER_HIP_OK) return rc;
-    rc = ouster_hip_destagger(ctx, st.dev(in), st.dev(out), h, w, elem_bytes, shifts, n_shifts, inverse, 1);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return st.finish();
-}
-
-int ouster_hip_cartesian_host(ouster_hip_ctx* ctx, const ouster_hip_lut* lut, const uint32_t* range, void* xyz,
-                              int xyz_dtype) {
-    if (!ctx || !lut) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!float_elem(xyz_dtype))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "xyz_dtype must be F32 or F64");
-    const size_t npx = (size_t)lut->w * lut->h;
-    if (npx == 0) return OUSTER_HIP_OK;
-    if (!range || !xyz) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL image pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    Staging st(ctx);
-    const auto in = st.input(range, npx * 4), out = st.output(xyz, npx * 3 * float_elem(xyz_dtype));
-    int rc = st.stage();
-    if (rc != OUSTER_HIP_OK) return rc;
-    rc = ouster_hip_cartesian(ctx, lut, (const uint32_t*)st.dev(in), st.dev(out), xyz_dtype, 1);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return st.finish();
-}
-
-int ouster_hip_dewarp_host(ouster_hip_ctx* ctx, const void* points, const double* poses, void* dewarped, int dtype,
-                           uint32_t h, uint32_t w) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (!float_elem(dtype)) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
-    if (h == 0 || w == 0) return OUSTER_HIP_OK;
-    if (!points || !poses || !dewarped) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t pbytes = (size_t)h * w * 3 * float_elem(dtype);
-    Staging st(ctx);
-    const auto in = st.input(points, pbytes), po = st.input(poses, (size_t)w * 128), out = st.output(dewarped, pbytes);
-    int rc = st.stage();
-    if (rc != OUSTER_HIP_OK) return rc;
-    rc = ouster_hip_dewarp(ctx, st.dev(in), (const double*)st.dev(po), st.dev(out), dtype, h, w, 1);
-    if (rc != OUSTER_HIP_OK) return rc;
-    return st.finish();
-}
-
-// ---- range-gated, compacting frame dewarp ------------------------------------------------------
-int ouster_hip_range_gate(double min_range, double max_range, uint32_t* min_r, uint32_t* max_r, int* empty) {
-    // uint32_t min_r = ceil(min_range * 1e3), max_r = floor(max_range * 1e3): dewarp_impl.h:33-34
-    const double lo = std::ceil(min_range * 1e3), hi = std::floor(max_range * 1e3);
-    const bool none = !(hi >= 0) || !(lo <= 4294967295.0) || hi < lo;
-    if (empty) *empty = none ? 1 : 0;
-    if (min_r) *min_r = (none || lo <= 0) ? 0u : (uint32_t)lo;
-    if (max_r) *max_r = none ? 0u : (hi >= 4294967295.0 ? 0xffffffffu : (uint32_t)hi);
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_dewarp_frames(ouster_hip_ctx* ctx, const ouster_hip_lut* const* luts, uint32_t n_luts,
-                             const uint32_t* range, const uint32_t* status,
-                             const uint64_t* timestamp, const double* poses, uint32_t n_frames,
-                             double min_range, double max_range, int dtype, void* points,
-                             uint32_t* frame_idxs, uint32_t* col_idxs, uint64_t* timestamps_ns,
-                             uint64_t capacity, uint64_t* frame_offsets) {
-    return ouster_hip_dewarp_frames_counted(ctx, luts, n_luts, range, status, timestamp, poses, n_frames, min_range,
-                                            max_range, dtype, points, frame_idxs, col_idxs, timestamps_ns, capacity,
-                                            frame_offsets, nullptr);
-}
-
-static int dewarp_frames_impl(ouster_hip_ctx* ctx, const ouster_hip_lut* const* luts, uint32_t n_luts,
-                              const uint32_t* range, const uint32_t* status,
-                              const uint64_t* timestamp, const double* poses, const float* pose_rows, uint32_t n_frames,
-                              double min_range, double max_range, int dtype, void* points,
-                              uint32_t* frame_idxs, uint32_t* col_idxs, uint64_t* timestamps_ns,
-                              uint64_t capacity, uint64_t* frame_offsets, const uint16_t* gate_counts) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (!float_elem(dtype))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
-    if (!luts || n_luts == 0) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at least one LUT is required");
-    for (uint32_t i = 0; i < n_luts; ++i) {
-        if (!luts[i]) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL LUT handle");
-        if (luts[i]->w != luts[0]->w || luts[i]->h != luts[0]->h)
-            return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "all LUTs of a batch must have the same dimensions");
-        if (luts[i]->separable != luts[0]->separable)
-            return fail(OUSTER_HIP_ERR_UNSUPPORTED, "cannot mix separable and full LUTs in one batch");
-    }
-    if (!frame_offsets) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "frame_offsets is NULL");
-    if (timestamps_ns && !timestamp)
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "timestamps_ns requested without column timestamps");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (n_frames == 0) {
-        HIP_TRY(hipMemsetAsync(frame_offsets, 0, sizeof(uint64_t), ctx->stream));
-        return OUSTER_HIP_OK;
-    }
-    if (pose_rows && (((uintptr_t)pose_rows) & 15u))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "pose_rows must be 16-byte aligned");
-    if (!range || !status || (!poses && !pose_rows) || (!points && capacity))
-        return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    const uint32_t w = luts[0]->w, h = luts[0]->h;
-    // uint32_t min_r = ceil(min_range * 1e3), max_r = floor(max_range * 1e3): dewarp_impl.h:33-34
-    const double lo = std::ceil(min_range * 1e3), hi = std::floor(max_range * 1e3);
-    if (!(hi >= 0) || !(lo <= 4294967295.0) || hi < lo) {  // nothing can pass the gate
-        HIP_TRY(hipMemsetAsync(frame_offsets, 0, sizeof(uint64_t) * ((size_t)n_frames + 1), ctx->stream));
-        return OUSTER_HIP_OK;
-    }
-    std::vector<LutDev> l(n_luts);
-    for (uint32_t i = 0; i < n_luts; ++i) l[i] = luts[i]->dev;
-    if (ensure_luts(ctx, l)) return fail(OUSTER_HIP_ERR_RUNTIME, "LUT descriptor upload failed");
-    // scratch: the three-kernel path's per-column offsets, then the single-pass path's tile words
-    const size_t col_off_bytes = ((size_t)n_frames * (w + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
-    const size_t tile_words = (size_t)n_frames * ((w + 63) / 64) + 128;
-    if (ctx->scratch.ensure(col_off_bytes + tile_words * 8))
-        return fail(OUSTER_HIP_ERR_RUNTIME, "scratch allocation failed");
-    DewarpFramesArgs a{};
-    a.range = range;
-    a.status = status;
-    a.timestamp = timestamp;
-    a.poses = poses;
-    a.pose_rows = pose_rows;
-    a.luts = (const LutDev*)ctx->luts.p;
-    a.n_luts = n_luts;
-    a.w = w;
-    a.h = h;
-    a.n_frames = n_frames;
-    a.min_r = lo <= 0 ? 0u : (uint32_t)lo;
-    a.max_r = hi >= 4294967295.0 ? 0xffffffffu : (uint32_t)hi;
-    a.dtype = dtype;
-    a.col_off = (uint32_t*)ctx->scratch.p;
-    a.gate_counts = gate_counts;
-#ifdef OUSTER_EXPERIMENTS
-    a.tile_state = (ctx->knobs.dewarp_single_pass && !gate_counts && !pose_rows) ? (uint64_t*)((uint8_t*)ctx->scratch.p + col_off_bytes) : nullptr;
-#else
-    a.tile_state = nullptr;   // the single-pass kernels are not in a default build (knob "dewarp_single_pass" is then without effect)
-#endif
-    a.frame_off = frame_offsets;
-    a.points = points;
-    a.frame_idxs = frame_idxs;
-    a.col_idxs = col_idxs;
-    a.timestamps_ns = timestamps_ns;
-    a.capacity = capacity;
-    HIP_TRY(launch_dewarp_frames(a, luts[0]->separable, ctx->stream, ctx->knobs.dwf_stream));
-    return OUSTER_HIP_OK;
-}
-
-int ouster_hip_dewarp_frames_counted(ouster_hip_ctx* ctx, const ouster_hip_lut* const* luts, uint32_t n_luts,
-                                     const uint32_t* range, const uint32_t* status,
-                                     const uint64_t* timestamp, const double* poses, uint32_t n_frames,
-                                     double min_range, double max_range, int dtype, void* points,
-                                     uint32_t* frame_idxs, uint32_t* col_idxs, uint64_t* timestamps_ns,
-                                     uint64_t capacity, uint64_t* frame_offsets, const uint16_t* gate_counts) {
-    return dewarp_frames_impl(ctx, luts, n_luts, range, status, timestamp, poses, nullptr, n_frames, min_range, max_range, dtype,
-                              points, frame_idxs, col_idxs, timestamps_ns, capacity, frame_offsets, gate_counts);
-}
-
-int ouster_hip_dewarp_frames_rows(ouster_hip_ctx* ctx, const ouster_hip_lut* const* luts, uint32_t n_luts,
-                                  const uint32_t* range, const uint32_t* status, const uint64_t* timestamp,
-                                  const float* pose_rows, uint32_t n_frames, double min_range, double max_range,
-                                  void* points, uint32_t* frame_idxs, uint32_t* col_idxs, uint64_t* timestamps_ns,
-                                  uint64_t capacity, uint64_t* frame_offsets, const uint16_t* gate_counts) {
-    if (!pose_rows && n_frames) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
-    return dewarp_frames_impl(ctx, luts, n_luts, range, status, timestamp, nullptr, pose_rows, n_frames, min_range, max_range,
-                              OUSTER_HIP_F32, points, frame_idxs, col_idxs, timestamps_ns, capacity, frame_offsets, gate_counts);
-}
-
-// ---- OSF field planes ---------------------------------------------------------------------------
-int ouster_hip_osf_unpack(ouster_hip_ctx* ctx, const ouster_hip_osf_plane* planes, uint32_t n_planes,
-                          uint32_t h, uint32_t w, const int32_t* pixel_shift_by_row) {
-    if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (n_planes == 0 || h == 0 || w == 0) return OUSTER_HIP_OK;
-    if (!planes) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "planes is NULL");
-    bool any_png = false;
-    size_t unfiltered_bytes = 0;          // device scratch for the planes that arrive as filtered PNG scanlines
-    uint32_t n_filtered = 0, max_row_bytes = 0;
-    for (uint32_t i = 0; i < n_planes; ++i) {
-        const ouster_hip_osf_plane& p = planes[i];
-        if (!p.src || !p.dst) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: NULL pointer", i);
-        const uint32_t e = p.dst_elem_size;
-        if (!(e == 1 || e == 2 || e == 4 || e == 8))
-            return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: unsupported element size %u", i, e);
-        if (p.flags & ~OUSTER_HIP_OSF_FLAG_FILTERED) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: unknown flags", i);
-        static const uint32_t want[6] = {0, 1, 2, 3, 4, 8};
-        if (p.encoding >= OUSTER_HIP_OSF_PNG_GRAY8 && p.encoding <= OUSTER_HIP_OSF_PNG_RGBA16) {
-            if (p.src_pixel_bytes != want[p.encoding])
-                return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: pixel size does not match its PNG type", i);
-            any_png = true;
-            if (p.flags & OUSTER_HIP_OSF_FLAG_FILTERED) {
-                ++n_filtered;
-                unfiltered_bytes += ((size_t)h * w * p.src_pixel_bytes + 15) & ~(size_t)15;
-                max_row_bytes = std::max(max_row_bytes, w * p.src_pixel_bytes);
-            }
-        } else if (p.encoding == OUSTER_HIP_OSF_ZPNG) {
-            if (p.src_pixel_bytes == 0 || p.src_pixel_bytes > 8)
-                return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: ZPNG pixels are 1..8 bytes", i);
-            if (p.flags) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: ZPNG planes carry no PNG filters", i);
-        } else {
-            return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "plane %u: unknown encoding %u", i, p.encoding);
-        }
-    }
-    if (n_filtered && osf_png_unfilter_lds_bytes(w, max_row_bytes) > 160u * 1024u)   // the launcher's own figure
-        return fail(OUSTER_HIP_ERR_UNSUPPORTED, "a PNG scanline of %u bytes needs %zu bytes of LDS for the device filters (160 KB per workgroup): "
-                    "hand the planes over unfiltered (flags = 0)", max_row_bytes, osf_png_unfilter_lds_bytes(w, max_row_bytes));
-    HIP_TRY(hipSetDevice(ctx->device));
-    OsfUnpackArgs a{};
-    a.h = h;
-    a.w = w;
-    if (any_png && pixel_shift_by_row) {  // stagger(img, px_offset) = destagger with inverse offsets
-        std::vector<int32_t> off;
-        dest_offsets(pixel_shift_by_row, h, w, 1, off);
-        if (ensure_offsets(ctx, off)) return fail(OUSTER_HIP_ERR_RUNTIME, "offset upload failed");
-        ctx->shifts_host.clear();
-        a.offsets = (const int32_t*)ctx->offsets.p;
-    }
-    // the job arrays: the unpack jobs (filtered planes read the device-side unfiltered copy), then the unfilter jobs
-    std::vector<ouster_hip_osf_plane> jobs(planes, planes + n_planes);
-    std::vector<OsfUnfilterJob> unf;
-    if (n_filtered) {
-        if (ctx->osf_pixels.ensure(unfiltered_bytes)) return fail(OUSTER_HIP_ERR_RUNTIME, "scratch allocation failed");
-        size_t at = 0;
-        for (uint32_t i = 0; i < n_planes; ++i) {
-            if (!(jobs[i].flags & OUSTER_HIP_OSF_FLAG_FILTERED)) continue;
-            OsfUnfilterJob j{};
-            j.raw = (const uint8_t*)jobs[i].src;
-            j.out = (uint8_t*)ctx->osf_pixels.p + at;
-            j.bpp = jobs[i].src_pixel_bytes;
-            unf.push_back(j);
-            jobs[i].src = j.out;
-            jobs[i].flags = 0;
-            at += ((size_t)h * w * j.bpp + 15) & ~(size_t)15;
-        }
-    }
-    const size_t bytes = (size_t)n_planes * sizeof(ouster_hip_osf_plane), ubytes = unf.size() * sizeof(OsfUnfilterJob);
-    if (ctx->scratch.ensure(bytes + ubytes)) return fail(OUSTER_HIP_ERR_RUNTIME, "scratch allocation failed");
-    HIP_TRY(hipMemcpyAsync(ctx->scratch.p, jobs.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (ubytes) HIP_TRY(hipMemcpyAsync((uint8_t*)ctx->scratch.p + bytes, unf.data(), ubytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the job arrays are this call's memory
-    if (n_filtered) {
-        OsfUnfilterArgs u{};
-        u.jobs = (const OsfUnfilterJob*)((uint8_t*)ctx->scratch.p + bytes);
-        u.h = h;
-        u.w = w;
-        HIP_TRY(launch_osf_png_unfilter(u, n_filtered, max_row_bytes, ctx->stream));
-    }
-    a.planes = (const ouster_hip_osf_plane*)ctx->scratch.p;
-    HIP_TRY(launch_osf_unpack(a, n_planes, ctx->stream));
     return OUSTER_HIP_OK;
 }
 

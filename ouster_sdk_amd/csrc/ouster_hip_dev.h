@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <type_traits>
 #include <utility>
@@ -178,6 +179,13 @@ hipError_t launch_slotmap(const DecodeArgs& a, int device, hipStream_t st);
 hipError_t launch_destagger(const DestaggerArgs& a, uint32_t n_images, hipStream_t st);
 hipError_t launch_cartesian(const CartesianArgs& a, int mode, hipStream_t st);
 hipError_t launch_dewarp(const DewarpArgs& a, hipStream_t st);
+// tile width of the standalone tiled kernels (launch_cartesian, launch_dewarp).  Unlike the 14-stream k_decode these one/two-stream
+// kernels gain nothing from 256-column tiles (same-box A/B: equal for f32, 5-10 % slower for f64 and
+// full-LUT), so 64 stays the default; OUSTER_HIP_CT_TILE=256 is kept for experiments.  (Hidden: not a symbol of the library.)
+__attribute__((visibility("hidden"))) inline uint32_t standalone_tile_width() {
+    static const int env = [] { const char* e = getenv("OUSTER_HIP_CT_TILE"); return e ? atoi(e) : 0; }();
+    return env == 256 ? 256u : 64u;
+}
 // stream_mode: -1 auto | 0 never | 1 always where eligible -- the persistent k_dwf_emit_stream instead of k_dwf_emit (knob "dwf_stream")
 hipError_t launch_dewarp_frames(const DewarpFramesArgs& a, bool separable, hipStream_t st, int stream_mode = -1);
 hipError_t launch_osf_unpack(const OsfUnpackArgs& a, uint32_t n_planes, hipStream_t st);

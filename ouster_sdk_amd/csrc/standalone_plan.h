@@ -1,6 +1,6 @@
 // standalone_plan.h -- which kernel and which launch shape ouster_hip_destagger / ouster_hip_cartesian / ouster_hip_dewarp
 // get: host integers in, values out.  Includes nothing but the standard library, so it compiles (and is tested) without
-// HIP, like decode_plan.h.  The launchers of k_standalone.hip call these functions and only launch.
+// HIP, like decode_plan.h.  The launchers of k_destagger.hip, k_cartesian.hip and k_dewarp.hip call these functions and only launch.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-"""GPU: ouster_hip_osf_unpack (k_osf_unpack, k_osf_png_unfilter of csrc/k_standalone.hip) called through the C ABI on planes the
+"""GPU: ouster_hip_osf_unpack (k_osf_unpack, k_osf_png_unfilter of csrc/k_osf.hip) called through the C ABI on planes the
 fixtures never hold -- ragged widths, every ZPNG pixel size (1..8 bytes), element sizes that differ from the pixel's, the
 stagger-back at widths that are no power of two, the unfilter kernel one pixel either side of its block / ring / band sizes and
 at its LDS limit, mixed jobs in one launch behind guard bytes, every rejected argument.

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import PCAPS, has_gpu
+from test_range_gate_cpu import IDS as RANGE_GATE_IDS, TABLE as RANGE_GATES
 
 pytestmark = pytest.mark.gpu
 
@@ -478,6 +479,51 @@ def test_dewarp_frames_matches_oracle(oracle, h, w, n, path):
                             capacity=cap)
     assert int(_np(got2["frame_offsets"])[-1]) == tot
     assert torch.equal(got2["points"][:cap], got["points"][:cap])
+
+
+@pytest.mark.parametrize("gate,expected", RANGE_GATES, ids=RANGE_GATE_IDS)
+def test_dewarp_frames_range_gates(oracle, gate, expected):
+    """The frame dewarp at the edges of its range gate (tests/test_range_gate_cpu.py has the arithmetic): 2 frames of 4 x 16, every
+    column valid, ranges from the values a threshold can sit on.  frame_offsets and the points are the oracle's; an empty gate
+    leaves frame_offsets all zeros.  The oracle converts its thresholds with a plain C cast, which is defined inside
+    [0, 2^32 - 1] only, so it is handed the gate clamped to that interval -- what the saturation does to a gate that is not empty."""
+    O = oracle
+    h, w, n = 4, 16, 2
+    min_r, max_r, empty = expected
+    rng = np.random.default_rng(5)
+    cal = O.synthetic_calib(h=h, w=w, b2l_x=15.806)
+    ldir, lofs = cal.xyz_lut(True)
+    hp = HotPath("RNG15_RFL8_NIR8", h, w, 4)
+    hp.add_lut(cal.beam_to_lidar, cal.lut_transform(True), cal.beam_azimuth_angles, cal.beam_altitude_angles)
+    r = rng.choice(np.array([0, 1, 2, 2000, 2500, 0xffffffff], np.uint32), size=(n, h, w))
+    status = np.ones((n, w), dtype=np.uint32)
+    ts = rng.integers(1, 2 ** 62, size=(n, w)).astype(np.uint64)
+    poses = np.tile(np.eye(4), (n, w, 1, 1))
+    ang = rng.uniform(-0.3, 0.3, size=(n, w))
+    poses[..., 0, 0] = np.cos(ang); poses[..., 0, 1] = -np.sin(ang)
+    poses[..., 1, 0] = np.sin(ang); poses[..., 1, 1] = np.cos(ang)
+    poses[..., :3, 3] = rng.uniform(-20, 20, size=(n, w, 3))
+    d_r, d_st, d_po = torch.from_numpy(r).cuda(), torch.from_numpy(status).cuda(), torch.from_numpy(poses).cuda()
+    lo, hi = gate
+    o_lo, o_hi = max(float(lo), 0.0), min(float(hi), 4294967.2951)   # floor(4294967.2951e3) == 2^32 - 1
+    for ldt, tdt, tol in ((np.float64, torch.float64, 1e-9), (np.float32, torch.float32, 1e-4)):
+        got = hp.dewarp_frames(d_r, d_st, d_po, lo, hi, dtype=tdt, provenance=False)
+        g_off = _np(got["frame_offsets"])
+        if empty:
+            assert np.array_equal(g_off, np.zeros(n + 1, np.uint64)), gate
+            continue
+        want = [O.dewarp_frame(r[k], status[k], ts[k], poses[k], ldir.astype(ldt), lofs.astype(ldt), o_lo, o_hi)[0] for k in range(n)]
+        kept = [int(((r[k] >= min_r) & (r[k] <= max_r)).sum()) for k in range(n)]
+        assert [len(x) for x in want] == kept, gate          # the clamped gate is the table's gate
+        offs = np.concatenate([[0], np.cumsum(kept)]).astype(np.uint64)
+        assert np.array_equal(g_off, offs), gate
+        tot = int(offs[-1])
+        if tot:
+            # the bars of test_dewarp_frames_matches_oracle are for points within 525 m (the f32 one is a few f32 roundings of
+            # such a value); range 0xffffffff lies 4.3e6 m out, so a point's bar grows with its own distance beyond 525 m
+            wp = np.concatenate(want).astype(np.float64)
+            bar = tol * np.maximum(1.0, np.abs(wp).max(axis=1, keepdims=True) / 525.0)
+            assert (np.abs(_np(got["points"])[:tot].astype(np.float64) - wp) <= bar).all(), gate
 
 
 @pytest.mark.parametrize("h,w", [(16, 100), (33, 1001), (7, 36), (128, 2048), (40, 1088)])

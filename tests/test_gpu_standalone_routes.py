@@ -1,4 +1,4 @@
-"""GPU: the launch routes of the standalone kernels (k_destagger*, k_cartesian*, k_dewarp* of k_standalone.hip) that small,
+"""GPU: the launch routes of the standalone kernels (k_destagger*, k_cartesian*, k_dewarp* of k_destagger / k_cartesian / k_dewarp.hip) that small,
 aligned, power-of-two inputs never take, each against the CPU oracle.
 
 Every test first asks the launch plan (ouster_sdk_amd/csrc/standalone_plan.cpp through tools/standalone_plan_tool) which route its

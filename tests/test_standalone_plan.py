@@ -1,5 +1,6 @@
 """CPU-only: the launch plan of the standalone kernels (ouster_sdk_amd/csrc/standalone_plan.cpp) against tables written by
-hand from the launchers of k_standalone.hip as they stood before the plan became a unit of its own.
+hand from the launchers (now in k_destagger.hip, k_cartesian.hip and k_dewarp.hip) as they stood before the plan became a unit
+of its own.
 
 tools/standalone_plan_tool.cpp -- g++ only, no HIP library -- evaluates plan_destagger / plan_cartesian / plan_dewarp; every
 expected value below was worked out on paper from these rules, not taken from the tool:
