@@ -15,12 +15,12 @@ HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++20 -fPIC -Wno-unused-result $(if $
 OBJ := $(CSRC)/_build
 SPEC_IDS := 0 1 2 3 4 5
 STREAM_IDS := 1 2 3 4 5
-FEATURES := image frame_ops pose normals voxel icp
+FEATURES := image tonemap frame_ops pose normals voxel icp
 # the standalone calls of the hot path, k_<name>.hip + capi_<name>.hip each; contracted like the decode (they are not in NO_CONTRACT).
 # k_dewarp_experiments.hip holds the frame dewarp's experimental kernels and is part of an EXPERIMENTS=1 build only.
 STANDALONE := destagger cartesian dewarp osf
-HIP_OBJS := $(foreach i,$(SPEC_IDS),$(OBJ)/k_decode_$(i).o) $(foreach i,$(STREAM_IDS),$(OBJ)/k_decode_stream_$(i).o) $(STANDALONE:%=$(OBJ)/k_%.o) $(if $(EXPERIMENTS),$(OBJ)/k_dewarp_experiments.o,) $(OBJ)/k_image.o $(OBJ)/k_frame_ops.o $(OBJ)/k_pose.o $(OBJ)/pose_util.o $(OBJ)/k_normals.o $(OBJ)/normals_util.o $(OBJ)/k_voxel.o $(OBJ)/voxel_util.o $(OBJ)/k_icp.o $(OBJ)/icp_util.o $(OBJ)/decode_launch.o $(OBJ)/decode_plan.o $(OBJ)/standalone_plan.o $(OBJ)/ouster_hip_capi.o $(STANDALONE:%=$(OBJ)/capi_%.o) $(FEATURES:%=$(OBJ)/capi_%.o) $(OBJ)/host_pool.o
-HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/standalone_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/dwf_dev.h $(CSRC)/wide_tile.h $(CSRC)/k_image.h $(CSRC)/k_frame_ops.h $(CSRC)/k_pose.h $(CSRC)/pose_host.h $(CSRC)/k_normals.h $(CSRC)/normals_host.h $(CSRC)/k_voxel.h $(CSRC)/voxel_host.h $(CSRC)/voxel_dev.h $(CSRC)/k_icp.h $(CSRC)/icp_host.h $(CSRC)/capi_internal.h $(CSRC)/carve.h include/ouster_hip.h
+HIP_OBJS := $(foreach i,$(SPEC_IDS),$(OBJ)/k_decode_$(i).o) $(foreach i,$(STREAM_IDS),$(OBJ)/k_decode_stream_$(i).o) $(STANDALONE:%=$(OBJ)/k_%.o) $(if $(EXPERIMENTS),$(OBJ)/k_dewarp_experiments.o,) $(OBJ)/k_image.o $(OBJ)/k_tonemap.o $(OBJ)/k_frame_ops.o $(OBJ)/k_pose.o $(OBJ)/pose_util.o $(OBJ)/k_normals.o $(OBJ)/normals_util.o $(OBJ)/k_voxel.o $(OBJ)/voxel_util.o $(OBJ)/k_icp.o $(OBJ)/icp_util.o $(OBJ)/decode_launch.o $(OBJ)/decode_plan.o $(OBJ)/standalone_plan.o $(OBJ)/ouster_hip_capi.o $(STANDALONE:%=$(OBJ)/capi_%.o) $(FEATURES:%=$(OBJ)/capi_%.o) $(OBJ)/host_pool.o
+HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/standalone_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/dwf_dev.h $(CSRC)/wide_tile.h $(CSRC)/k_image.h $(CSRC)/k_tonemap.h $(CSRC)/tonemap_dev.h $(CSRC)/k_frame_ops.h $(CSRC)/k_pose.h $(CSRC)/pose_host.h $(CSRC)/k_normals.h $(CSRC)/normals_host.h $(CSRC)/k_voxel.h $(CSRC)/voxel_host.h $(CSRC)/voxel_dev.h $(CSRC)/k_icp.h $(CSRC)/icp_host.h $(CSRC)/capi_internal.h $(CSRC)/carve.h include/ouster_hip.h
 ROCM ?= /opt/rocm
 CXXFLAGS := -O2 -std=c++17 -fPIC -pthread -Wall -Wextra -Iinclude -I$(CSRC)/host -I$(ROCM)/include -D__HIP_PLATFORM_AMD__
 
@@ -41,12 +41,13 @@ $(OBJ)/k_decode_%.o: $(CSRC)/k_decode.hip $(HIP_HDRS)
 
 # no FMA contraction in kernels held to models that round every step on its own, none in their plain C++ halves (host/*_util.cpp):
 #   k_image      the display images round like the reference's host build
+#   k_tonemap    LocalToneMapper and the luminance percentiles equal tests/tonemap_model.py
 #   k_frame_ops  compares converted values only; kept so that no later arithmetic can feed a comparison fused
 #   k_pose       interp_pose / transform equal tests/pose_model.py
 #   k_normals    normals equals tests/normals_model.py
 #   k_voxel      the sums are left folds of single IEEE operations (tests/voxel_model.py)
 #   k_icp        correspondences, residuals, median and the terms of the sums equal tests/icp_model.py
-NO_CONTRACT := k_image k_frame_ops k_pose k_normals k_voxel k_icp
+NO_CONTRACT := k_image k_tonemap k_frame_ops k_pose k_normals k_voxel k_icp
 $(NO_CONTRACT:%=$(OBJ)/%.o): HIPFLAGS += -ffp-contract=off
 
 $(OBJ)/%.o: $(CSRC)/%.hip $(HIP_HDRS)
@@ -88,6 +89,8 @@ oracle:
 
 cpptests: $(LIB)/libouster_core_amd.so
 	$(MAKE) -C tests/cpp -s
+	$(MAKE) -C tests/cpp -s -f tonemap.mk tonemap
+	$(MAKE) -C tests/cpp -s -f tonemap.mk tonemap_ref_sanitized   # runs it: the host half under ASan / UBSan
 	$(MAKE) -C oracle -s refcpptests
 
 clean:

@@ -47,6 +47,7 @@ using EigenX3R = Eigen::Array<T, Eigen::Dynamic, 3, Eigen::RowMajor>;
 #endif
 
 template <typename T> class ImgRef;
+template <typename T> class RgbImgRef;
 template <typename T> class VecRef;
 
 namespace impl {
@@ -369,6 +370,51 @@ class ImgRef {
     bool any() const { return count() != 0; }
 
    private:
+    T* p_;
+    size_t rows_, cols_;
+};
+
+/** Non-owning view of an H x W x 3 image, row-major with the three channels of a pixel next to each other; stands in for
+ *  Eigen::TensorMap<rgb_img_t<T>> (ouster_core/include/ouster/core/typedefs.h of the reference). */
+template <typename T>
+class RgbImgRef {
+   public:
+    using NC = typename std::remove_const<T>::type;
+    RgbImgRef(T* data, size_t rows, size_t cols) : p_(data), rows_(rows), cols_(cols) {}
+    template <typename U = T, typename = typename std::enable_if<std::is_const<U>::value>::type>
+    RgbImgRef(const RgbImgRef<NC>& o) : p_(o.data()), rows_(o.rows()), cols_(o.cols()) {}
+#ifdef OUSTER_HIP_USE_EIGEN
+    /** A view of an Eigen::TensorMap (or Tensor) of rank 3, row-major, whose last dimension is 3; a temporary TensorMap binds,
+     *  as it does where the reference takes the TensorMap by value.
+     *  @throw std::invalid_argument for another layout or channel count */
+    template <typename D, typename = typename std::enable_if<
+                              std::is_same<typename D::Scalar, NC>::value && D::NumDimensions == 3 &&
+                              std::is_convertible<decltype(std::declval<const D&>().data()), T*>::value>::type>
+    RgbImgRef(const D& t) : p_(t.data()), rows_(static_cast<size_t>(t.dimension(0))), cols_(static_cast<size_t>(t.dimension(1))) {
+        check_tensor<D>(t.dimension(2));
+    }
+    /** ... and of a Tensor lvalue that owns its memory (its const data() would give no mutable view) */
+    template <typename D, typename = typename std::enable_if<
+                              !std::is_const<D>::value && std::is_same<typename D::Scalar, NC>::value && D::NumDimensions == 3 &&
+                              !std::is_convertible<decltype(std::declval<const D&>().data()), T*>::value &&
+                              std::is_convertible<decltype(std::declval<D&>().data()), T*>::value>::type>
+    RgbImgRef(D& t) : p_(t.data()), rows_(static_cast<size_t>(t.dimension(0))), cols_(static_cast<size_t>(t.dimension(1))) {
+        check_tensor<D>(t.dimension(2));
+    }
+#endif
+    T* data() const { return p_; }
+    size_t rows() const { return rows_; }
+    size_t cols() const { return cols_; }
+    size_t size() const { return rows_ * cols_ * 3; }   ///< elements
+    T& operator()(size_t r, size_t c, size_t ch) const { return p_[(r * cols_ + c) * 3 + ch]; }
+
+   private:
+#ifdef OUSTER_HIP_USE_EIGEN
+    template <typename D> static void check_tensor(std::ptrdiff_t channels) {
+        if (static_cast<int>(D::Layout) != static_cast<int>(Eigen::RowMajor) || channels != 3)
+            throw std::invalid_argument("RgbImgRef: the tensor is not a row-major H x W x 3 image");
+    }
+#endif
     T* p_;
     size_t rows_, cols_;
 };

@@ -194,7 +194,8 @@ int ouster_hip_ctx_device(ouster_hip_ctx* ctx); /* the HIP device ordinal the co
  *   "stream" -1 auto | 0 never | 128/256 force k_decode_stream's tile width   "stream_rows" rows of its tiles
  *   "stream_wait" 0: trust the in-order vmcnt instead of draining it before a prefetched tile is used
  *   "stream_min_tiles" tiles per persistent workgroup below which a launch stays on the one-tile kernels
- *   "pose_direct" 1: k_pose_interp stores every lane's own row instead of staging a workgroup's rows in LDS (A/B) */
+ *   "pose_direct" 1: k_pose_interp stores every lane's own row instead of staging a workgroup's rows in LDS (A/B)
+ *   "tonemap_bands" 1 .. 64: workgroups per tile of k_tm_hist (bands of the tile's rows) | 0 the launch's own choice (A/B) */
 int ouster_hip_ctx_set_knob(ouster_hip_ctx* ctx, const char* name, int value);
 int ouster_hip_sync(ouster_hip_ctx* ctx);
 const char* ouster_hip_last_error(void);
@@ -487,6 +488,55 @@ int ouster_hip_image_percentiles_host(ouster_hip_ctx* ctx, const void* image, in
                                       void* lo_hi);
 int ouster_hip_image_apply_host(ouster_hip_ctx* ctx, void* image, int dtype, uint32_t h, uint32_t w, const void* dark,
                                 const ouster_hip_image_map* map);
+
+/* ---- display images: the RGB overloads of AutoExposure, LocalToneMapper ------------------------------ */
+/* The device half of AutoExposure::update on RGB images (src/image_processing.cpp:307-405) and of LocalToneMapper
+ * (:532-710), batched: n_images images of h x w pixels of 3 interleaved elements, image i at images + i * image_stride ELEMENTS
+ * (0: dense, 3 * h * w).  in_type is F32 or F64 and then equal to out_type, or F16 with out_type F32: FLOAT16 bit patterns,
+ * converted by the reference's integer formula (:59-65: 0 and 0x7e00 give 0, everything else uint32(bits + 0x1C000) << 13 read
+ * as a float -- not an IEEE conversion; any pattern gives a finite float).  out_type (F32 / F64) is the type T the reference
+ * would run in: every value below is computed in T step by step, bit for bit.  The frame-to-frame state stays with the caller,
+ * in double (include/ouster/core/image_processing.h).  n_images <= 65535, h * w <= 2^31; float / double elements must be finite.
+ *
+ * ouster_hip_image_lum_percentiles: the order statistics of :312-348 / :538-568.  The sample is the luminance
+ *   (r * T(0.299) + g * T(0.587)) + b * T(0.114) of pixels 0, 4, 8, ... of the flat pixel index, kept when > 0:
+ *   n [n_images] = its size, lo_hi [n_images][2] of T = its floor(n * lo_percentile)-th and (n - floor(n * hi_percentile) - 1)-th
+ *   smallest values (0, 0 when n == 0).  n < 100 is reported like any other n.  Needs lo_percentile + hi_percentile < 1.
+ *   For the RGB AutoExposure the map that follows is ouster_hip_image_apply over the image seen as h x 3w elements; that call
+ *   takes in_type F16 with out_type F32 as well (map NONE: the plain converted image).
+ * ouster_hip_image_tonemap: everything of LocalToneMapper::apply after its state machine (:586-689), per image from one record
+ *   of the DEVICE array params [n_images]: the map WITHOUT a clamp, dynamic-range compression where `compress`, Reinhard, the
+ *   8 x 8 tile tables of 1024 bins (clip limit 1, excess and CDF summed in bin order in float), their bilinear blend
+ *   (extrapolating in the outer half tiles, as the reference does) and the saturation pass with
+ *   color_factor = T(0.75) * T(color_ramp).  map.mode NONE is the reference's early return: the image is left alone, or
+ *   converted / copied when out is another buffer.  out may be images itself when in_type == out_type and the strides agree.
+ *   Refused with INVALID_ARGUMENT: NULL pointers, a type pair other than the three above, a stride smaller than an image, and
+ *   h < 8 or w < 8 (the reference has empty tiles there and blends NaN tables into the image: a deliberate deviation).
+ *   UNSUPPORTED: a tile of more than 2^24 pixels (the reference's float counts stop counting there).
+ *   The histograms and tables (2 x 256 KB per image) live in the context's grow-only workspace. */
+typedef struct ouster_hip_tonemap_params {
+    ouster_hip_image_map map;  /* mode NONE / SCALE / AFFINE with sub, mul, add; use_dark is ignored */
+    int32_t compress;          /* 1: hi_state < compress_dr_max_lum */
+    int32_t color_correct;     /* 0: scale by lum_clahe / lum_ae only */
+    double color_ramp;         /* max(0, (hi_state - 0.5) / 0.5) while hi_state < 1, else 1; the kernel rounds it to T and
+                                  multiplies T(0.75) by it, in T as the reference does */
+} ouster_hip_tonemap_params;
+int ouster_hip_image_lum_percentiles(ouster_hip_ctx* ctx, const void* images, int in_type, int out_type, uint32_t n_images,
+                                     uint32_t h, uint32_t w, size_t image_stride, double lo_percentile, double hi_percentile,
+                                     uint32_t* n, void* lo_hi);
+int ouster_hip_image_tonemap(ouster_hip_ctx* ctx, const void* images, int in_type, void* out, int out_type, uint32_t n_images,
+                             uint32_t h, uint32_t w, size_t in_stride, size_t out_stride,
+                             const ouster_hip_tonemap_params* params);
+/* The same on ONE host image, results in HOST memory when the call returns: pool memory is worked on in place, other memory goes
+ * through the context's scratch.  params / map: HOST records.  out may be image itself when the types match.
+ * ouster_hip_image_apply_rgb_host is the RGB AutoExposure's second half: ouster_hip_image_apply on the h x 3w view, with the
+ * FLOAT16 conversion on load (a NULL map or mode NONE: the converted image, nothing when out == image). */
+int ouster_hip_image_lum_percentiles_host(ouster_hip_ctx* ctx, const void* image, int in_type, int out_type, uint32_t h,
+                                          uint32_t w, double lo_percentile, double hi_percentile, uint32_t* n, void* lo_hi);
+int ouster_hip_image_tonemap_host(ouster_hip_ctx* ctx, const void* image, int in_type, void* out, int out_type, uint32_t h,
+                                  uint32_t w, const ouster_hip_tonemap_params* params);
+int ouster_hip_image_apply_rgb_host(ouster_hip_ctx* ctx, const void* image, int in_type, void* out, int out_type, uint32_t h,
+                                    uint32_t w, const ouster_hip_image_map* map);
 
 /* ---- frame_ops: clip / filter / mask / beam selection ------------------------------------------------ */
 /* The device half of ouster::sdk::core::frame_ops (ouster_core/include/ouster/core/frame_ops.h, src/frame_ops.cpp), batched:

@@ -83,6 +83,11 @@ class ImageMap(C.Structure):
 IMAGE_MAP_NONE, IMAGE_MAP_SCALE, IMAGE_MAP_AFFINE = 0, 1, 2
 
 
+class TonemapParams(C.Structure):
+    """ouster_hip_tonemap_params (include/ouster_hip.h): the per-image record of ouster_hip_image_tonemap"""
+    _fields_ = [("map", ImageMap), ("compress", C.c_int32), ("color_correct", C.c_int32), ("color_ramp", C.c_double)]
+
+
 class FopsPlane(C.Structure):
     """ouster_hip_fops_plane (include/ouster_hip.h): one plane of a frame_ops call"""
     _fields_ = [("data", C.c_void_p), ("twin", C.c_void_p), ("image_stride", C.c_size_t), ("type", C.c_int32),
@@ -172,6 +177,9 @@ ABI_SYMBOLS = [
     # display images: the device half of BeamUniformityCorrector / AutoExposure
     "ouster_hip_image_dark_rows", "ouster_hip_image_percentiles", "ouster_hip_image_apply",
     "ouster_hip_image_dark_rows_host", "ouster_hip_image_percentiles_host", "ouster_hip_image_apply_host",
+    # RGB display images: the device half of AutoExposure's RGB overloads and of LocalToneMapper
+    "ouster_hip_image_lum_percentiles", "ouster_hip_image_tonemap", "ouster_hip_image_lum_percentiles_host",
+    "ouster_hip_image_tonemap_host", "ouster_hip_image_apply_rgb_host",
     # frame_ops: clip / filter / mask / beam selection
     "ouster_hip_frame_ops_invalid_bits", "ouster_hip_frame_ops_clip", "ouster_hip_frame_ops_invalidate",
     "ouster_hip_frame_ops_select_rows", "ouster_hip_frame_ops_clip_host", "ouster_hip_frame_ops_invalidate_host",
@@ -292,6 +300,14 @@ def load_hip(private_path: Optional[str] = None):
         L.ouster_hip_image_dark_rows_host.argtypes = [vp, vp, C.c_int, u32, u32, vp, vp]
         L.ouster_hip_image_percentiles_host.argtypes = [vp, vp, C.c_int, u32, u32, vp, C.c_double, C.c_double, vp, vp]
         L.ouster_hip_image_apply_host.argtypes = [vp, vp, C.c_int, u32, u32, vp, vp]
+    if hasattr(L, "ouster_hip_image_tonemap"):   # absent only in older A/B builds loaded via OUSTER_HIP_SO
+        u32 = C.c_uint32
+        L.ouster_hip_image_lum_percentiles.argtypes = [vp, vp, C.c_int, C.c_int, u32, u32, u32, C.c_size_t, C.c_double, C.c_double,
+                                                       vp, vp]
+        L.ouster_hip_image_tonemap.argtypes = [vp, vp, C.c_int, vp, C.c_int, u32, u32, u32, C.c_size_t, C.c_size_t, vp]
+        L.ouster_hip_image_lum_percentiles_host.argtypes = [vp, vp, C.c_int, C.c_int, u32, u32, C.c_double, C.c_double, vp, vp]
+        L.ouster_hip_image_tonemap_host.argtypes = [vp, vp, C.c_int, vp, C.c_int, u32, u32, vp]
+        L.ouster_hip_image_apply_rgb_host.argtypes = [vp, vp, C.c_int, vp, C.c_int, u32, u32, vp]
     if hasattr(L, "ouster_hip_frame_ops_clip"):   # absent only in older A/B builds loaded via OUSTER_HIP_SO
         u32 = C.c_uint32
         L.ouster_hip_frame_ops_invalid_bits.argtypes = [C.c_int, C.c_double, C.POINTER(C.c_uint64)]

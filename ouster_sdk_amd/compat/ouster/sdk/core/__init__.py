@@ -9,6 +9,7 @@ from .data import ColHeader  # noqa: E402,F401  (a Python Enum in the reference 
 Packet = _core.LidarPacket      # the base class of the reference's packet types; only lidar packets exist here
 AutoExposure = _core.AutoExposure                        # ouster.sdk.core.AutoExposure / BeamUniformityCorrector of the reference
 BeamUniformityCorrector = _core.BeamUniformityCorrector
+LocalToneMapper = _core.LocalToneMapper                  # tone-maps the RGB field of the colour profiles for display
 SensorInfo = _core.SensorInfo   # SensorInfo(json_text) is a constructor of the C++ class (csrc/host/metadata.cpp)
 # voxel down-sampling on the GPU (csrc/k_voxel.hip): the reference's four names
 voxel_downsample_3d = _core.voxel_downsample_3d

@@ -8,19 +8,21 @@ namespace {
 size_t image_elem(int t) {
     switch (t) {
         case OUSTER_HIP_U8: return 1;
-        case OUSTER_HIP_U16: return 2;
+        case OUSTER_HIP_U16: case OUSTER_HIP_F16: return 2;
         case OUSTER_HIP_U32: case OUSTER_HIP_F32: return 4;
         case OUSTER_HIP_F64: return 8;
         default: return 0;
     }
 }
 // shared argument checks; fills what every image kernel needs.  Returns 1 when there is nothing to do.
+// f16_ok: FLOAT16 patterns with out_type F32 pass as well (ouster_hip_image_apply alone converts them)
 int image_args(ouster_hip_ctx* ctx, const void* planes, int in_type, int out_type, uint32_t n_images, uint32_t h, uint32_t w,
-               size_t image_stride, ImageArgs& a) {
+               size_t image_stride, ImageArgs& a, bool f16_ok = false) {
     if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
     if (!float_elem(out_type))
         return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "out_type must be F32 or F64");
-    if (in_type != OUSTER_HIP_U8 && in_type != OUSTER_HIP_U16 && in_type != OUSTER_HIP_U32 && in_type != out_type)
+    if (in_type != OUSTER_HIP_U8 && in_type != OUSTER_HIP_U16 && in_type != OUSTER_HIP_U32 && in_type != out_type &&
+        !(f16_ok && in_type == OUSTER_HIP_F16 && out_type == OUSTER_HIP_F32))
         return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "in_type must be U8, U16, U32 or out_type");
     if (n_images == 0 || h == 0 || w == 0) return 1;
     if (n_images > 65535u) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "at most 65535 images per call");
@@ -81,7 +83,7 @@ int ouster_hip_image_apply(ouster_hip_ctx* ctx, const void* planes, int in_type,
                            uint32_t h, uint32_t w, size_t in_stride, size_t out_stride, const void* dark,
                            const ouster_hip_image_map* maps) {
     ImageArgs a;
-    const int rc = image_args(ctx, planes, in_type, out_type, n_images, h, w, in_stride, a);
+    const int rc = image_args(ctx, planes, in_type, out_type, n_images, h, w, in_stride, a, true);
     if (rc) return rc > 0 ? OUSTER_HIP_OK : rc;
     if (!out) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "out is NULL");
     if (out_stride && out_stride < (size_t)h * w) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "out_stride smaller than an image");

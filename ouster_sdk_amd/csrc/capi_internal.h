@@ -100,6 +100,7 @@ struct ouster_hip_ctx {
     bool own_stream = false;
     DevBuf state, tile_valid, offsets, luts, counts, scratch, slotmap, hdrw, osf_pixels;
     DevBuf image_mask;                   // ouster_hip_image_dark_rows: the column masks of a batch
+    DevBuf tonemap_ws;                   // ouster_hip_image_tonemap: tile histograms and look-up tables, 2 x 256 KB per image
     DevBuf tables;                       // upload_table: the small host table of the call in flight (shifts, row indices, pose segments, ...)
     void* table_pin = nullptr;           //   ... its page-locked staging, and the event behind its last copy
     size_t table_pin_cap = 0;

@@ -39,6 +39,7 @@ const KnobDef knob_table[] = {
     {"dwf_stream", "OUSTER_HIP_DWF_STREAM", &Knobs::dwf_stream},   // the frame dewarp's emit kernel: -1 auto | 0 k_dwf_emit | 1 the persistent k_dwf_emit_stream where eligible
     {"stream_loader", "OUSTER_HIP_STREAM_LOADER", &Knobs::stream_loader},   // loader waves of k_decode_stream2 (0 = k_decode_stream: every wave fetches)
     {"pose_direct", "OUSTER_HIP_POSE_DIRECT", &Knobs::pose_direct},   // 1 = k_pose_interp stores each lane's own row (128 B lane stride) instead of going through LDS (A/B)
+    {"tonemap_bands", "OUSTER_HIP_TONEMAP_BANDS", &Knobs::tonemap_bands},   // k_tm_hist: workgroups (bands of rows) per tile, 1 .. 64; 0 = the launch's own choice (A/B)
 };
 const int knob_count = (int)(sizeof knob_table / sizeof knob_table[0]);
 

@@ -95,6 +95,7 @@ struct Knobs {
     int stream = -1, stream_rows = 0, stream_wait = 1, stream_min_tiles = 8, stream_order = 0, slotmap = 1;
     int dwf_stream = -1, stream_loader = 4;
     int pose_direct = 0;
+    int tonemap_bands = 0;
 };
 struct KnobDef {
     const char* name;    // ouster_hip_ctx_set_knob

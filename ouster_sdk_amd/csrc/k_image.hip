@@ -16,6 +16,7 @@
 // is bit-exact.  Every arithmetic step is one IEEE operation in the image type: no contraction in this file.
 #pragma clang fp contract(off)
 #include "k_image.h"
+#include "tonemap_dev.h"
 
 #include <stdint.h>
 #include <type_traits>
@@ -26,82 +27,6 @@
 
 namespace ouster_hip_dev {
 namespace {
-
-template <class T> struct KeyOf;
-template <> struct KeyOf<float> { typedef uint32_t type; };
-template <> struct KeyOf<double> { typedef uint64_t type; };
-
-__device__ __forceinline__ uint32_t f_bits(float v) { return __float_as_uint(v); }
-__device__ __forceinline__ uint64_t f_bits(double v) { return (uint64_t)__double_as_longlong(v); }
-__device__ __forceinline__ float bits_f(uint32_t b) { return __uint_as_float(b); }
-__device__ __forceinline__ double bits_f(uint64_t b) { return __longlong_as_double((long long)b); }
-
-// total order of the non-NaN values as unsigned integers: negatives are complemented, the others get the top bit
-template <class K> __device__ __forceinline__ K ordered_key(K b) {
-    constexpr K top = (K)1 << (sizeof(K) * 8 - 1);
-    return (b & top) ? (K)~b : (K)(b | top);
-}
-template <class K> __device__ __forceinline__ K ordered_key_inv(K k) {
-    constexpr K top = (K)1 << (sizeof(K) * 8 - 1);
-    return (k & top) ? (K)(k ^ top) : (K)~k;
-}
-
-// four consecutive input elements as one load (u8: 4 B, u16: 8 B, 32-bit: 16 B, f64: 2 x 16 B)
-template <class TIN> struct __attribute__((aligned(sizeof(TIN) * 4 > 16 ? 16 : sizeof(TIN) * 4))) Vec4 { TIN v[4]; };
-
-// histogram[d] += 1 for every lane with `valid`, called by whole waves.  Lanes of one wave that hit the same LDS word are served
-// one after the other, and display data is full of ties (8-bit planes, a shared exponent in the top digit), so the two
-// most frequent digits of a wave -- the first pending lane's, twice -- go as ONE add of their lane count; what is left adds
-// for itself.
-__device__ __forceinline__ void hist_add(uint32_t* hist, uint32_t d, bool valid) {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint64_t rem = __builtin_amdgcn_ballot_w64(valid);
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        if (rem == 0) break;   // wave-uniform
-        const uint32_t lead = (uint32_t)__builtin_ctzll(rem);
-        const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)d, (int)lead);
-        const bool mine = valid && d == d0;
-        const uint64_t m = __builtin_amdgcn_ballot_w64(mine);
-        if (lane == lead) atomicAdd(&hist[d0], (uint32_t)__popcll(m));
-        if (mine) valid = false;
-        rem &= ~m;
-    }
-    if (valid) atomicAdd(&hist[d], 1u);
-}
-
-// One wave finds the bin of rank k in a 256-bin histogram kept as NSUB partial histograms: lane l owns bins 4l .. 4l + 3.
-// Writes sel[0] = bin, sel[1] = rank inside the bin, sel[2] = total count.
-template <int NSUB>
-__device__ __forceinline__ void select_bin(const uint32_t (*hist)[256], uint32_t k, uint32_t* sel) {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t c[4], tot = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        c[j] = 0;
-#pragma unroll
-        for (int s = 0; s < NSUB; ++s) c[j] += hist[s][4 * lane + j];
-        tot += c[j];
-    }
-    uint32_t inc = tot;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d, 64);
-        if (lane >= (uint32_t)d) inc += t;
-    }
-    uint32_t run = inc - tot;
-    if (k >= run && k < inc) {   // exactly one lane while k < total
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (k >= run && k < run + c[j]) {
-                sel[0] = 4 * lane + j;
-                sel[1] = k - run;
-            }
-            run += c[j];
-        }
-    }
-    if (lane == 63) sel[2] = inc;
-}
 
 // ------------------------------------------------------------------------------------
 // k_img_colmask: thread = column, walks the rows (a wave reads 64 consecutive elements per row); one ballot per wave is
@@ -199,85 +124,24 @@ __global__ __launch_bounds__(256) void k_img_dark_rows(ImageArgs a) {
 // their bit patterns.  Both order statistics are selected in the same passes (two histograms once their prefixes differ).
 // The sample of a 128 x 2048 image (65 536 values) does not fit LDS, so every digit pass reads it again: the plane was written
 // by the previous kernel and the passes follow each other at once, so all but the first come from L2 / MALL.
-// n is reported as it is (also below 100: the host decides); n == 0 gives lo = hi = 0.
+// n is reported as it is (also below 100: the host decides); n == 0 gives lo = hi = 0.  The selection itself is k_image.h's
+// select_percentiles, which k_tm_lum_percentiles runs over luminances.
 // ------------------------------------------------------------------------------------
 template <class TIN, class T>
 __global__ __launch_bounds__(1024) void k_img_percentiles(ImageArgs a) {
-    typedef typename KeyOf<T>::type K;
-    constexpr int KB = sizeof(K) * 8, UNR = 4;
-    __shared__ uint32_t s_hist[2][4][256];
-    __shared__ uint32_t s_sel[2][3];
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, img = blockIdx.x;
-    const uint32_t w = a.w, hw = a.h * a.w, nsamp = (hw + 3) / 4;
+    const uint32_t img = blockIdx.x, w = a.w, hw = a.h * a.w;
     const TIN* in = (const TIN*)a.in + (size_t)img * a.in_stride;
     const T* dark = a.dark ? (const T*)a.dark + (size_t)img * a.h : nullptr;
-    uint32_t k[2] = {0, 0}, n = 0;
-    K prefix[2] = {0, 0};
-    for (int shift = KB - 8; shift >= 0; shift -= 8) {
-        const bool first = shift == KB - 8;
-        const bool same = prefix[0] == prefix[1];   // uniform: one histogram serves both
-        for (uint32_t i = tid; i < 2 * 4 * 256; i += 1024) (&s_hist[0][0][0])[i] = 0;
-        __syncthreads();
-        for (uint32_t base = 0; base < nsamp; base += 1024 * UNR) {
-            T v[UNR];
-            uint32_t rowv[UNR];
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const uint32_t j = base + u * 1024 + tid;
-                v[u] = (T)0;
-                rowv[u] = 0;
-                if (j < nsamp) {
-                    v[u] = (T)in[(size_t)j * 4];
-                    if (dark) rowv[u] = (j * 4) / w;
-                }
+    select_percentiles<T>(
+        [&](uint32_t j) {
+            T x = (T)in[(size_t)j * 4];
+            if (dark) {
+                x = x - dark[(j * 4) / w];
+                x = x < (T)0 ? (T)0 : x;
             }
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                T x = v[u];
-                if (dark) {
-                    x = x - dark[rowv[u]];
-                    x = x < (T)0 ? (T)0 : x;
-                }
-                const bool pos = x > (T)0;   // lanes past the sample hold 0
-                const K key = f_bits(x);
-                const uint32_t d = (uint32_t)(key >> shift) & 255u;
-                bool m0 = pos, m1 = pos;
-                if (!first) {
-                    const K hi = (K)(key >> (shift + 8));
-                    m0 = pos && hi == prefix[0];
-                    m1 = pos && hi == prefix[1];
-                }
-                hist_add(s_hist[0][wave & 3u], d, m0);
-                if (!same) hist_add(s_hist[1][wave & 3u], d, m1);
-            }
-        }
-        __syncthreads();
-        if (first) {
-            if (wave == 0) select_bin<4>(s_hist[0], 0u, s_sel[0]);   // sel[2] = n
-            __syncthreads();
-            n = s_sel[0][2];
-            if (n == 0) break;
-            // the reference's indices: floor(n * lo_percentile) and n - floor(n * hi_percentile) - 1, products in double
-            const uint32_t tl = (uint32_t)((double)n * a.lo_percentile), th = (uint32_t)((double)n * a.hi_percentile);
-            k[0] = tl < n ? tl : n - 1;
-            k[1] = th + 1 <= n ? n - th - 1 : 0;
-            __syncthreads();
-        }
-        if (wave == 0) select_bin<4>(s_hist[0], k[0], s_sel[0]);
-        if (wave == 1) select_bin<4>(same ? s_hist[0] : s_hist[1], k[1], s_sel[1]);
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            prefix[s] = (K)(prefix[s] << 8) | (K)s_sel[s][0];
-            k[s] = s_sel[s][1];
-        }
-    }
-    if (tid == 0) {
-        a.n_positive[img] = n;
-        T* o = (T*)a.lo_hi + (size_t)img * 2;
-        o[0] = n ? bits_f(prefix[0]) : (T)0;
-        o[1] = n ? bits_f(prefix[1]) : (T)0;
-    }
+            return x;
+        },
+        (hw + 3) / 4, a.lo_percentile, a.hi_percentile, &a.n_positive[img], (T*)a.lo_hi + (size_t)img * 2);
 }
 
 // ------------------------------------------------------------------------------------
@@ -417,6 +281,11 @@ hipError_t launch_image_apply(const ImageArgs& a, int in_type, int out_type, hip
     const uint32_t nchunk = (a.h * a.w + 3) / 4, want = (nchunk + 255) / 256;
     uint32_t cap = 8192 / a.n_images;
     if (cap < 8) cap = 8;
+    if (in_type == OUSTER_HIP_F16) {   // FLOAT16 patterns (the RGB planes): tonemap_dev.h's integer formula on load
+        if (out_type != OUSTER_HIP_F32) return hipErrorInvalidValue;
+        k_img_apply<F16Bits, float><<<dim3(want < cap ? want : cap, a.n_images), 256, 0, st>>>(a);
+        return hipGetLastError();
+    }
     return by_types(in_type, out_type, [&](auto tin, auto t) {
         k_img_apply<decltype(tin), decltype(t)><<<dim3(want < cap ? want : cap, a.n_images), 256, 0, st>>>(a);
         return hipGetLastError();

@@ -123,6 +123,7 @@ void ouster_hip_ctx_destroy(ouster_hip_ctx* c) {
     c->hdrw.release();
     c->osf_pixels.release();
     c->image_mask.release();
+    c->tonemap_ws.release();
     c->tables.release();
     c->normals_pairs.release();
     c->voxel_ws.release();

@@ -1035,11 +1035,72 @@ PYBIND11_MODULE(core, m) {
                 throw py::error_already_set();
             }
         };
-        auto bind_update = [guarded](auto& cls) {
+        // an H x W x 3 array as the view the RGB overloads take; any other shape is the reference's ValueError
+        auto rgb_ref = [](auto& image) {
+            using T = typename std::remove_reference<decltype(image)>::type::value_type;
+            if (image.ndim() != 3 || image.shape(2) != 3) throw std::invalid_argument("Expected an H x W x 3 array");
+            return RgbImgRef<T>(image.mutable_data(), static_cast<size_t>(image.shape(0)), static_cast<size_t>(image.shape(1)));
+        };
+        // update(float16 H x W x 3) -> a new float32 array (python/src/cpp/client/processing.cpp:802-823, :862-883 of the reference)
+        auto bind_update_f16 = [guarded](auto& cls) {
+            using C = typename std::remove_reference<decltype(cls)>::type::type;
+            cls.def(
+                "update",
+                [guarded](C& self, const py::array& image, bool update_state) -> py::array {
+                    if (image.dtype().kind() != 'f' || image.itemsize() != 2 || !(image.flags() & py::array::c_style))
+                        throw py::type_error("update: expected a C-contiguous float32, float64 or float16 image");
+                    if (image.ndim() != 3 || image.shape(2) != 3) throw std::invalid_argument("Expected an H x W x 3 array");
+                    const size_t h = static_cast<size_t>(image.shape(0)), w = static_cast<size_t>(image.shape(1));
+                    py::array_t<float> out(std::vector<py::ssize_t>{image.shape(0), image.shape(1), 3});
+                    RgbImgRef<const float16_t> in(static_cast<const float16_t*>(image.data()), h, w);
+                    RgbImgRef<float> o(out.mutable_data(), h, w);
+                    guarded([&] { self.update(in, o, update_state); });
+                    return out;
+                },
+                py::arg("image").noconvert(), py::arg("update_state") = true);
+        };
+        // extension: update_batch on a host stack (n, h, w, 3) of float16 patterns or images of the output type
+        auto run_batch_rgb = [guarded](auto& self, const py::array& images_in, bool f64, bool update_state) -> py::array {
+            namespace oh = ouster::sdk::hip;
+            using C = typename std::remove_reference<decltype(self)>::type;
+            py::array images = py::array::ensure(images_in, py::array::c_style);
+            if (!images || images.ndim() != 4 || images.shape(3) != 3) throw std::invalid_argument("Expected an N x H x W x 3 array");
+            const py::ssize_t isz = images.itemsize();
+            ChanFieldType t;
+            if (images.dtype().kind() == 'f' && isz == 2 && !f64) t = ChanFieldType::FLOAT16;
+            else if (images.dtype().kind() == 'f' && isz == (f64 ? 8 : 4)) t = f64 ? ChanFieldType::FLOAT64 : ChanFieldType::FLOAT32;
+            else throw py::type_error("update_batch: images must be float16 (float32 output) or of the output dtype");
+            const std::vector<py::ssize_t> shape = {images.shape(0), images.shape(1), images.shape(2), 3};
+            const uint32_t n = static_cast<uint32_t>(shape[0]), h = static_cast<uint32_t>(shape[1]), w = static_cast<uint32_t>(shape[2]);
+            py::array out = f64 ? py::array(py::array_t<double>(shape)) : py::array(py::array_t<float>(shape));
+            if (images.size() == 0) return out;
+            guarded([&] {
+                std::shared_ptr<oh::Context> ctx = oh::Context::current();
+                oh::ScopedContext on_ctx(ctx);
+                oh::DeviceBuffer din(static_cast<size_t>(images.nbytes())), dout(static_cast<size_t>(out.nbytes()));
+                din.upload(images.data(), static_cast<size_t>(images.nbytes()));
+                auto call = [&](auto* o) {
+                    if constexpr (std::is_same<C, oi::AutoExposure>::value) self.update_batch_rgb(*ctx, din.data(), t, n, h, w, o, update_state);
+                    else self.update_batch(*ctx, din.data(), t, n, h, w, o, update_state);
+                };
+                if (f64) call(static_cast<double*>(dout.data()));
+                else call(static_cast<float*>(dout.data()));
+                dout.download(out.mutable_data(), static_cast<size_t>(out.nbytes()));
+            });
+            return out;
+        };
+        auto bind_update = [guarded, rgb_ref](auto& cls) {
             using C = typename std::remove_reference<decltype(cls)>::type::type;
             cls.def(
                    "update",
-                   [guarded](C& self, py::array_t<float, py::array::c_style> image, bool update_state) {
+                   [guarded, rgb_ref](C& self, py::array_t<float, py::array::c_style> image, bool update_state) {
+                       if constexpr (std::is_same<C, oi::AutoExposure>::value) {
+                           if (image.ndim() == 3) {   // the RGB overload: H x W x 3, in place
+                               RgbImgRef<float> rgb = rgb_ref(image);
+                               guarded([&] { self.update(rgb, update_state); });
+                               return;
+                           }
+                       }
                        if (image.ndim() != 2) throw py::type_error("update: expected a 2-D image");
                        ImgRef<float> ref(image.mutable_data(), static_cast<size_t>(image.shape(0)), static_cast<size_t>(image.shape(1)));
                        guarded([&] { self.update(ref, update_state); });
@@ -1047,7 +1108,14 @@ PYBIND11_MODULE(core, m) {
                    py::arg("image").noconvert(), py::arg("update_state") = true)
                 .def(
                     "update",
-                    [guarded](C& self, py::array_t<double, py::array::c_style> image, bool update_state) {
+                    [guarded, rgb_ref](C& self, py::array_t<double, py::array::c_style> image, bool update_state) {
+                        if constexpr (std::is_same<C, oi::AutoExposure>::value) {
+                            if (image.ndim() == 3) {
+                                RgbImgRef<double> rgb = rgb_ref(image);
+                                guarded([&] { self.update(rgb, update_state); });
+                                return;
+                            }
+                        }
                         if (image.ndim() != 2) throw py::type_error("update: expected a 2-D image");
                         ImgRef<double> ref(image.mutable_data(), static_cast<size_t>(image.shape(0)), static_cast<size_t>(image.shape(1)));
                         guarded([&] { self.update(ref, update_state); });
@@ -1097,7 +1165,9 @@ PYBIND11_MODULE(core, m) {
             .def_property_readonly("hi_state", &oi::AutoExposure::hi_state)
             .def_property_readonly("initialized", &oi::AutoExposure::initialized);
         bind_update(ae);
-        ae.def("update_batch", [run_batch](oi::AutoExposure& self, const py::array& planes, bool float64, bool update_state) {
+        bind_update_f16(ae);
+        ae.def("update_batch", [run_batch, run_batch_rgb](oi::AutoExposure& self, const py::array& planes, bool float64, bool update_state) {
+            if (planes.ndim() == 4) return run_batch_rgb(self, planes, float64, update_state);   // (n, h, w, 3): the RGB overloads
             return run_batch(self, planes, float64, update_state, nullptr);
         }, py::arg("planes"), py::arg("float64") = false, py::arg("update_state") = true);
         py::class_<oi::BeamUniformityCorrector> buc(m, "BeamUniformityCorrector");
@@ -1110,6 +1180,38 @@ PYBIND11_MODULE(core, m) {
         buc.def("update_batch", [run_batch](oi::BeamUniformityCorrector& self, const py::array& planes, bool float64, bool update_state,
                                             oi::AutoExposure* then) { return run_batch(self, planes, float64, update_state, then); },
                 py::arg("planes"), py::arg("float64") = false, py::arg("update_state") = true, py::arg("then") = nullptr);
+
+        // LocalToneMapper (python/src/cpp/client/processing.cpp:836-883 of the reference): a Python bool selects compress_dr, a
+        // float compress_dr_max_lum.  update(float16 H x W x 3) returns a new float32 array; the float32 / float64 forms work in
+        // place (an extension: the reference binds the float16 form only).
+        py::class_<oi::LocalToneMapper> ltm(m, "LocalToneMapper");
+        ltm.def(py::init<>())
+            .def(py::init<int>(), py::arg("update_every"))
+            .def(py::init<double, double, int, double, bool, bool>(), py::arg("lo_percentile"), py::arg("hi_percentile"),
+                 py::arg("update_every"), py::arg("damping"), py::arg("compress_dr"), py::arg("color_correct"))
+            .def(py::init<double, double, int, double, double, bool>(), py::arg("lo_percentile"), py::arg("hi_percentile"),
+                 py::arg("update_every"), py::arg("damping"), py::arg("compress_dr_max_lum"), py::arg("color_correct"))
+            .def_property_readonly("lo_state", &oi::LocalToneMapper::lo_state)   // extensions: the state, read-only
+            .def_property_readonly("hi_state", &oi::LocalToneMapper::hi_state)
+            .def_property_readonly("initialized", &oi::LocalToneMapper::initialized);
+        ltm.def(
+               "update",
+               [guarded, rgb_ref](oi::LocalToneMapper& self, py::array_t<float, py::array::c_style> image, bool update_state) {
+                   RgbImgRef<float> rgb = rgb_ref(image);
+                   guarded([&] { self.update(rgb, update_state); });
+               },
+               py::arg("image").noconvert(), py::arg("update_state") = true)
+            .def(
+                "update",
+                [guarded, rgb_ref](oi::LocalToneMapper& self, py::array_t<double, py::array::c_style> image, bool update_state) {
+                    RgbImgRef<double> rgb = rgb_ref(image);
+                    guarded([&] { self.update(rgb, update_state); });
+                },
+                py::arg("image").noconvert(), py::arg("update_state") = true);
+        bind_update_f16(ltm);
+        ltm.def("update_batch", [run_batch_rgb](oi::LocalToneMapper& self, const py::array& images, bool float64, bool update_state) {
+            return run_batch_rgb(self, images, float64, update_state);
+        }, py::arg("images"), py::arg("float64") = false, py::arg("update_state") = true);
     }
 
     // streaming pipeline for host-side packets (include/ouster/hip/frame_stream.h; extension over the
