@@ -3,10 +3,10 @@
 // takes is decided by decode_plan.cpp.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <stdint.h>
 
 #include "kernels_common.h"
+#include "launch_util.h"
 
 namespace ouster_hip_dev {
 
@@ -129,14 +129,8 @@ __global__ __launch_bounds__(256) void k_slotmap(DecodeArgs a) {
 hipError_t launch_slotmap(const DecodeArgs& a, int device, hipStream_t st) {
     const size_t lds = slotmap_lds_bytes(a.g.columns_per_frame, a.g.columns_per_packet, a.slots_per_frame);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    static std::atomic<uint32_t> granted[16];
-    if (lds > 48 * 1024 && granted[device & 15].load(std::memory_order_acquire) < lds) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_slotmap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        granted[device & 15].store((uint32_t)lds, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(k_slotmap, dim3(a.n_frames), dim3(256), lds, st, a);
-    return hipGetLastError();
+    static LdsGrant grant;
+    return launch_with_lds(k_slotmap, dim3(a.n_frames), dim3(256), lds, device, st, grant, a);
 }
 
 }  // namespace ouster_hip_dev

@@ -36,9 +36,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 
 #include "kernels_common.h"
+#include "launch_util.h"
 #include "wide_tile.h"
 
 #ifndef OUSTER_SPEC_ID
@@ -502,77 +502,16 @@ __global__ __launch_bounds__(256) void k_decode_wide_fixup(DecodeArgs a) {
 // ------------------------------------------------------------------------------------
 // launchers (host)
 // ------------------------------------------------------------------------------------
-// dynamic LDS above 48 KB needs the kernel's attribute raised (per kernel and device); remembered so
-// the steady state makes no runtime call
-struct LdsGrant {
-    std::atomic<uint32_t> bytes[16];
-    LdsGrant() { for (auto& b : bytes) b.store(0); }
-};
-template <class K>
-static hipError_t allow_lds(K kernel, size_t lds, int device, LdsGrant& g) {
-    if (lds <= 48 * 1024) return hipSuccess;
-    std::atomic<uint32_t>& have = g.bytes[device & 15];
-    if (have.load(std::memory_order_acquire) >= lds) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) have.store((uint32_t)lds, std::memory_order_release);
-    return e;
-}
-
-template <class S, int TILE, int XYZM>
-static hipError_t launch_decode_x(const DecodeArgs& a, dim3 grid, size_t lds, int device, hipStream_t st) {
-    if constexpr (XYZM == 1 || XYZM == 2) {
-        if (a.xyz_poses) {
-            static LdsGrant done_p;
-            hipError_t e = allow_lds(k_decode<S, TILE, XYZM, true>, lds, device, done_p);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_decode<S, TILE, XYZM, true>), grid, dim3(256), lds, st, a);
-            return hipGetLastError();
-        }
+// the kernel families of launch_ladder (launch_util.h): every one has a POSES form and takes full LUTs (XYZM 3)
+#define OUSTER_KERNEL_FAMILY(name, k)                                                                        \
+    struct name {                                                                                            \
+        template <class S, int T, int XYZM, bool POSES> static constexpr auto kernel = k<S, T, XYZM, POSES>; \
+        static constexpr bool poses = true, xyzm3 = true;                                                    \
     }
-    static LdsGrant done;
-    hipError_t e = allow_lds(k_decode<S, TILE, XYZM>, lds, device, done);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_decode<S, TILE, XYZM>), grid, dim3(256), lds, st, a);
-    return hipGetLastError();
-}
-
-template <class S, int TILE>
-static hipError_t launch_decode_t(const DecodeArgs& a, int xyzm, dim3 grid, size_t lds, int device, hipStream_t st) {
-    switch (xyzm) {
-        case 0: return launch_decode_x<S, TILE, 0>(a, grid, lds, device, st);
-        case 1: return launch_decode_x<S, TILE, 1>(a, grid, lds, device, st);
-        case 2: return launch_decode_x<S, TILE, 2>(a, grid, lds, device, st);
-        default: return launch_decode_x<S, TILE, 3>(a, grid, lds, device, st);
-    }
-}
-
-template <class S, int TILE, int XYZM>
-static hipError_t launch_fixup_x(const DecodeArgs& a, dim3 grid, size_t lds, int device, hipStream_t st) {
-    if constexpr (XYZM == 1 || XYZM == 2) {
-        if (a.xyz_poses) {
-            static LdsGrant done_p;
-            hipError_t e = allow_lds(k_decode_fixup<S, TILE, XYZM, true>, lds, device, done_p);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_decode_fixup<S, TILE, XYZM, true>), grid, dim3(256), lds, st, a);
-            return hipGetLastError();
-        }
-    }
-    static LdsGrant done;
-    hipError_t e = allow_lds(k_decode_fixup<S, TILE, XYZM>, lds, device, done);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_decode_fixup<S, TILE, XYZM>), grid, dim3(256), lds, st, a);
-    return hipGetLastError();
-}
-
-template <class S, int TILE>
-static hipError_t launch_fixup_t(const DecodeArgs& a, int xyzm, dim3 grid, size_t lds, int device, hipStream_t st) {
-    switch (xyzm) {
-        case 0: return launch_fixup_x<S, TILE, 0>(a, grid, lds, device, st);
-        case 1: return launch_fixup_x<S, TILE, 1>(a, grid, lds, device, st);
-        case 2: return launch_fixup_x<S, TILE, 2>(a, grid, lds, device, st);
-        default: return launch_fixup_x<S, TILE, 3>(a, grid, lds, device, st);
-    }
-}
+OUSTER_KERNEL_FAMILY(DecodeK, k_decode);
+OUSTER_KERNEL_FAMILY(FixupK, k_decode_fixup);
+OUSTER_KERNEL_FAMILY(WideK, k_decode_wide);
+OUSTER_KERNEL_FAMILY(WideFixupK, k_decode_wide_fixup);
 
 // bytes of the tile's pose table (ouster_hip_frame_out::xyz_poses): 12 values of the xyz element type per column
 static size_t pose_lds_bytes(const DecodeArgs& a, int xyzm, int cols) {
@@ -581,6 +520,7 @@ static size_t pose_lds_bytes(const DecodeArgs& a, int xyzm, int cols) {
 
 hipError_t OUSTER_SPEC_FN(launch_decode)(const DecodeArgs& a_in, int tile, int xyzm, int device, hipStream_t st) {
     const uint32_t tpf = a_in.tiles_per_frame;
+    const bool poses = a_in.xyz_poses != nullptr;
     if (a_in.mode == MODE_FIXUP) {
         DecodeArgs a = a_in;
         const size_t body = decode_lds_bytes(a.g, tile, true, a.beam_lds != 0, a.slots_per_frame);
@@ -593,9 +533,9 @@ hipError_t OUSTER_SPEC_FN(launch_decode)(const DecodeArgs& a_in, int tile, int x
         // row_chunks carries the number of workgroups the device keeps resident (2 per CU)
         const dim3 grid((uint32_t)std::min<uint64_t>(items, a.row_chunks ? a.row_chunks : 512u));
         switch (tile) {
-            case 64: return launch_fixup_t<SpecT, 64>(a, xyzm, grid, lds, device, st);
-            case 32: return launch_fixup_t<SpecT, 32>(a, xyzm, grid, lds, device, st);
-            default: return launch_fixup_t<SpecT, 16>(a, xyzm, grid, lds, device, st);
+            case 64: return launch_ladder<FixupK, SpecT, 64>(xyzm, poses, grid, dim3(256), lds, device, st, a);
+            case 32: return launch_ladder<FixupK, SpecT, 32>(xyzm, poses, grid, dim3(256), lds, device, st, a);
+            default: return launch_ladder<FixupK, SpecT, 16>(xyzm, poses, grid, dim3(256), lds, device, st, a);
         }
     }
     DecodeArgs a = a_in;
@@ -606,37 +546,9 @@ hipError_t OUSTER_SPEC_FN(launch_decode)(const DecodeArgs& a_in, int tile, int x
     lds += pose_lds_bytes(a, xyzm, tile);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     switch (tile) {
-        case 64: return launch_decode_t<SpecT, 64>(a, xyzm, grid, lds, device, st);
-        case 32: return launch_decode_t<SpecT, 32>(a, xyzm, grid, lds, device, st);
-        default: return launch_decode_t<SpecT, 16>(a, xyzm, grid, lds, device, st);
-    }
-}
-
-template <class S, int TW, int XYZM>
-static hipError_t launch_decode_wide_x(const DecodeArgs& a, dim3 grid, size_t lds, int device, hipStream_t st) {
-    if constexpr (XYZM == 1 || XYZM == 2) {
-        if (a.xyz_poses) {
-            static LdsGrant done_p;
-            hipError_t e = allow_lds(k_decode_wide<S, TW, XYZM, true>, lds, device, done_p);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_decode_wide<S, TW, XYZM, true>), grid, dim3(256), lds, st, a);
-            return hipGetLastError();
-        }
-    }
-    static LdsGrant done;
-    hipError_t e = allow_lds(k_decode_wide<S, TW, XYZM>, lds, device, done);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_decode_wide<S, TW, XYZM>), grid, dim3(256), lds, st, a);
-    return hipGetLastError();
-}
-
-template <class S, int TW>
-static hipError_t launch_decode_wide_t(const DecodeArgs& a, int xyzm, dim3 grid, size_t lds, int device, hipStream_t st) {
-    switch (xyzm) {
-        case 0: return launch_decode_wide_x<S, TW, 0>(a, grid, lds, device, st);
-        case 1: return launch_decode_wide_x<S, TW, 1>(a, grid, lds, device, st);
-        case 2: return launch_decode_wide_x<S, TW, 2>(a, grid, lds, device, st);
-        default: return launch_decode_wide_x<S, TW, 3>(a, grid, lds, device, st);
+        case 64: return launch_ladder<DecodeK, SpecT, 64>(xyzm, poses, grid, dim3(256), lds, device, st, a);
+        case 32: return launch_ladder<DecodeK, SpecT, 32>(xyzm, poses, grid, dim3(256), lds, device, st, a);
+        default: return launch_ladder<DecodeK, SpecT, 16>(xyzm, poses, grid, dim3(256), lds, device, st, a);
     }
 }
 
@@ -696,69 +608,15 @@ __global__ __launch_bounds__(256) void k_decode_wide_resolved(DecodeArgs a) {
     wide_tile<S, TW, XYZM, POSES, true>(a, smem, f, tile, rc, L.pix, L.hdr, a.rows_per_tile, a.row_chunks, true);
 }
 
-template <class S, int TW, int XYZM>
-static hipError_t launch_wide_resolved_x(const DecodeArgs& a, dim3 grid, size_t lds, int device, hipStream_t st) {
-    if constexpr (XYZM == 1 || XYZM == 2) {
-        if (a.xyz_poses) {
-            static LdsGrant done_p;
-            hipError_t e = allow_lds(k_decode_wide_resolved<S, TW, XYZM, true>, lds, device, done_p);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_decode_wide_resolved<S, TW, XYZM, true>), grid, dim3(256), lds, st, a);
-            return hipGetLastError();
-        }
-    }
-    static LdsGrant done;
-    hipError_t e = allow_lds(k_decode_wide_resolved<S, TW, XYZM>, lds, device, done);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_decode_wide_resolved<S, TW, XYZM>), grid, dim3(256), lds, st, a);
-    return hipGetLastError();
-}
-
-template <class S, int TW>
-static hipError_t launch_wide_resolved_t(const DecodeArgs& a, int xyzm, dim3 grid, size_t lds, int device, hipStream_t st) {
-    switch (xyzm) {
-        case 0: return launch_wide_resolved_x<S, TW, 0>(a, grid, lds, device, st);
-        case 1: return launch_wide_resolved_x<S, TW, 1>(a, grid, lds, device, st);
-        case 2: return launch_wide_resolved_x<S, TW, 2>(a, grid, lds, device, st);
-        default: return launch_wide_resolved_x<S, TW, 3>(a, grid, lds, device, st);
-    }
-}
+OUSTER_KERNEL_FAMILY(WideResolvedK, k_decode_wide_resolved);
 #endif  // OUSTER_EXPERIMENTS
-
-template <class S, int TW, int XYZM>
-static hipError_t launch_wide_fixup_x(const DecodeArgs& a, dim3 grid, size_t lds, int device, hipStream_t st) {
-    if constexpr (XYZM == 1 || XYZM == 2) {
-        if (a.xyz_poses) {
-            static LdsGrant done_p;
-            hipError_t e = allow_lds(k_decode_wide_fixup<S, TW, XYZM, true>, lds, device, done_p);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_decode_wide_fixup<S, TW, XYZM, true>), grid, dim3(256), lds, st, a);
-            return hipGetLastError();
-        }
-    }
-    static LdsGrant done;
-    hipError_t e = allow_lds(k_decode_wide_fixup<S, TW, XYZM>, lds, device, done);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_decode_wide_fixup<S, TW, XYZM>), grid, dim3(256), lds, st, a);
-    return hipGetLastError();
-}
-
-template <class S, int TW>
-static hipError_t launch_wide_fixup_t(const DecodeArgs& a, int xyzm, dim3 grid, size_t lds, int device, hipStream_t st) {
-    switch (xyzm) {
-        case 0: return launch_wide_fixup_x<S, TW, 0>(a, grid, lds, device, st);
-        case 1: return launch_wide_fixup_x<S, TW, 1>(a, grid, lds, device, st);
-        case 2: return launch_wide_fixup_x<S, TW, 2>(a, grid, lds, device, st);
-        default: return launch_wide_fixup_x<S, TW, 3>(a, grid, lds, device, st);
-    }
-}
 
 // a.mode == MODE_FIXUP: the persistent fix-up grid (a.row_chunks etc. describe its tiles, a.fast_tiles the optimistic pass's
 // column tiles, `resident` the workgroups the device keeps resident); otherwise one workgroup per tile
 hipError_t OUSTER_SPEC_FN(launch_decode_wide)(const DecodeArgs& a_in, int tw, int xyzm, int device, hipStream_t st, uint32_t resident) {
     DecodeArgs a = a_in;
     const uint32_t bpf = a.tiles_per_frame * a.row_chunks;
-    const bool fix = a.mode == MODE_FIXUP, resolved = a.mode == MODE_RESOLVED;
+    const bool fix = a.mode == MODE_FIXUP, resolved = a.mode == MODE_RESOLVED, poses = a.xyz_poses != nullptr;
     a.wide_img_words = (uint32_t)tw * (a.lds_col_slot >> 2) + 4u;
     if (fix || resolved)   // resolve_frame's scratch lies under the tile image
         a.wide_img_words = std::max<uint32_t>(a.wide_img_words, (uint32_t)((slotmap_lds_bytes(a.g.columns_per_frame, a.g.columns_per_packet, a.slots_per_frame) / 4 + 3) & ~(size_t)3));
@@ -775,8 +633,8 @@ hipError_t OUSTER_SPEC_FN(launch_decode_wide)(const DecodeArgs& a_in, int tw, in
         const uint64_t items = (uint64_t)a.n_frames * bpf;
         const dim3 grid((uint32_t)std::min<uint64_t>(items, resident ? resident : 512u));
         switch (tw) {   // 128 or 256 columns (narrower frames take k_decode_fixup): every width is 12 more kernels per profile to compile
-            case 128: return launch_wide_fixup_t<SpecT, 128>(a, xyzm, grid, lds, device, st);
-            case 256: return launch_wide_fixup_t<SpecT, 256>(a, xyzm, grid, lds, device, st);
+            case 128: return launch_ladder<WideFixupK, SpecT, 128>(xyzm, poses, grid, dim3(256), lds, device, st, a);
+            case 256: return launch_ladder<WideFixupK, SpecT, 256>(xyzm, poses, grid, dim3(256), lds, device, st, a);
             default: return hipErrorInvalidValue;
         }
     }
@@ -785,8 +643,8 @@ hipError_t OUSTER_SPEC_FN(launch_decode_wide)(const DecodeArgs& a_in, int tw, in
     if (resolved) {
 #ifdef OUSTER_EXPERIMENTS
         switch (tw) {
-            case 128: return launch_wide_resolved_t<SpecT, 128>(a, xyzm, grid, lds, device, st);
-            case 256: return launch_wide_resolved_t<SpecT, 256>(a, xyzm, grid, lds, device, st);
+            case 128: return launch_ladder<WideResolvedK, SpecT, 128>(xyzm, poses, grid, dim3(256), lds, device, st, a);
+            case 256: return launch_ladder<WideResolvedK, SpecT, 256>(xyzm, poses, grid, dim3(256), lds, device, st, a);
             default: return hipErrorInvalidValue;
         }
 #else
@@ -794,10 +652,10 @@ hipError_t OUSTER_SPEC_FN(launch_decode_wide)(const DecodeArgs& a_in, int tw, in
 #endif
     }
     switch (tw) {
-        case 64: return launch_decode_wide_t<SpecT, 64>(a, xyzm, grid, lds, device, st);
-        case 128: return launch_decode_wide_t<SpecT, 128>(a, xyzm, grid, lds, device, st);
-        case 512: return launch_decode_wide_t<SpecT, 512>(a, xyzm, grid, lds, device, st);
-        default: return launch_decode_wide_t<SpecT, 256>(a, xyzm, grid, lds, device, st);
+        case 64: return launch_ladder<WideK, SpecT, 64>(xyzm, poses, grid, dim3(256), lds, device, st, a);
+        case 128: return launch_ladder<WideK, SpecT, 128>(xyzm, poses, grid, dim3(256), lds, device, st, a);
+        case 512: return launch_ladder<WideK, SpecT, 512>(xyzm, poses, grid, dim3(256), lds, device, st, a);
+        default: return launch_ladder<WideK, SpecT, 256>(xyzm, poses, grid, dim3(256), lds, device, st, a);
     }
 }
 

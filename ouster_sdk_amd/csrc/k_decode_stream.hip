@@ -27,9 +27,8 @@
 // consecutive blocks (ncell is odd for the 8 and 16 B/px profiles -> 4-way bank conflicts at worst instead of 16).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "kernels_common.h"
+#include "launch_util.h"
 
 #ifndef OUSTER_SPEC_ID
 #error "compile with -DOUSTER_SPEC_ID=1..5"
@@ -564,57 +563,24 @@ __global__ __launch_bounds__(768) void k_decode_stream2(DecodeArgs a, StreamArgs
 // ------------------------------------------------------------------------------------
 // launcher (host)
 // ------------------------------------------------------------------------------------
-struct LdsGrantS {
-    std::atomic<uint32_t> bytes[16];
-    LdsGrantS() { for (auto& b : bytes) b.store(0); }
+// the kernel families of launch_ladder (launch_util.h): no POSES form, and full LUTs (XYZM 3) are read in the row loop -- not a
+// streaming candidate, refused
+struct StreamK {
+    template <class S, int TW, int XYZM, bool> static constexpr auto kernel = k_decode_stream<S, TW, XYZM>;
+    static constexpr bool poses = false, xyzm3 = false;
 };
-
-template <class S, int TW, int XYZM>
-static hipError_t launch_stream_x(const DecodeArgs& a, const StreamArgs& sp, dim3 grid, int device, hipStream_t st) {
-    static LdsGrantS done;
-    std::atomic<uint32_t>& have = done.bytes[device & 15];
-    if (sp.lds_bytes > 48 * 1024 && have.load(std::memory_order_acquire) < sp.lds_bytes) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_decode_stream<S, TW, XYZM>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.lds_bytes);
-        if (e != hipSuccess) return e;
-        have.store(sp.lds_bytes, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_decode_stream<S, TW, XYZM>), grid, dim3(512), sp.lds_bytes, st, a, sp);
-    return hipGetLastError();
-}
-
-template <class S, int TW, int XYZM>
-static hipError_t launch_stream2_x(const DecodeArgs& a, const StreamArgs& sp, dim3 grid, int device, hipStream_t st) {
-    static LdsGrantS done;
-    std::atomic<uint32_t>& have = done.bytes[device & 15];
-    if (sp.lds_bytes > 48 * 1024 && have.load(std::memory_order_acquire) < sp.lds_bytes) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_decode_stream2<S, TW, XYZM>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.lds_bytes);
-        if (e != hipSuccess) return e;
-        have.store(sp.lds_bytes, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_decode_stream2<S, TW, XYZM>), grid, dim3(512u + 64u * sp.loader), sp.lds_bytes, st, a, sp);
-    return hipGetLastError();
-}
+struct Stream2K {   // with loader waves: 128- and 256-column tiles only
+    template <class S, int TW, int XYZM, bool> static constexpr auto kernel = k_decode_stream2<S, TW, XYZM>;
+    static constexpr bool poses = false, xyzm3 = false;
+};
 
 template <class S, int TW>
 static hipError_t launch_stream_t(const DecodeArgs& a, const StreamArgs& sp, int xyzm, dim3 grid, int device, hipStream_t st) {
     if constexpr (TW == 128 || TW == 256) {
-        if (sp.loader) {
-            switch (xyzm) {
-                case 0: return launch_stream2_x<S, TW, 0>(a, sp, grid, device, st);
-                case 1: return launch_stream2_x<S, TW, 1>(a, sp, grid, device, st);
-                case 2: return launch_stream2_x<S, TW, 2>(a, sp, grid, device, st);
-                default: return hipErrorInvalidValue;
-            }
-        }
+        if (sp.loader)
+            return launch_ladder<Stream2K, S, TW>(xyzm, false, grid, dim3(512u + 64u * sp.loader), sp.lds_bytes, device, st, a, sp);
     }
-    switch (xyzm) {
-        case 0: return launch_stream_x<S, TW, 0>(a, sp, grid, device, st);
-        case 1: return launch_stream_x<S, TW, 1>(a, sp, grid, device, st);
-        case 2: return launch_stream_x<S, TW, 2>(a, sp, grid, device, st);
-        default: return hipErrorInvalidValue;   // full LUTs are read in the row loop: not a streaming candidate
-    }
+    return launch_ladder<StreamK, S, TW>(xyzm, false, grid, dim3(512), sp.lds_bytes, device, st, a, sp);
 }
 
 hipError_t OUSTER_SPEC_FN(launch_decode_stream)(const DecodeArgs& a, const StreamArgs& sp, int tw, int xyzm, int device,

@@ -13,6 +13,7 @@
 
 #include "dwf_dev.h"
 #include "kernels_common.h"
+#include "launch_util.h"
 
 namespace ouster_hip_dev {
 
@@ -576,13 +577,11 @@ bool launch_dwf_single_pass(const DewarpFramesArgs& a, bool separable, hipStream
         hipError_t e = hipMemsetAsync(a.tile_state, 0, ((size_t)a.n_frames * tiles + DWF_WORDS) * 8, st);
         if (e != hipSuccess) return e;
         const dim3 grid(a.n_frames * tiles);
-        auto go = [&](auto kernel) -> hipError_t {
-            if (lds > 48 * 1024) {
-                hipError_t ee = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (ee != hipSuccess) return ee;
-            }
-            hipLaunchKernelGGL(kernel, grid, dim3(DWF_NT), lds, st, a);
-            return hipGetLastError();
+        static LdsGrant grants[4];   // one per k_dwf_single instantiation below
+        auto go = [&](auto kernel, LdsGrant& grant) -> hipError_t {
+            int device = -1;   // not remembered if the runtime cannot say
+            (void)hipGetDevice(&device);
+            return launch_with_lds(kernel, grid, dim3(DWF_NT), lds, device, st, grant, a);
         };
         if (a.h <= 128) {   // the rebuilt single pass: static LDS, k_dwf_emit's tile
             auto fused = [&](auto rows) -> hipError_t {
@@ -599,8 +598,8 @@ bool launch_dwf_single_pass(const DewarpFramesArgs& a, bool separable, hipStream
             return a.h > 64 ? fused(std::integral_constant<int, 128>{}) : fused(std::integral_constant<int, 64>{});
         }
         if (a.dtype == OUSTER_HIP_F32)
-            return separable ? go(k_dwf_single<float, true, DWF_NT>) : go(k_dwf_single<float, false, DWF_NT>);
-        return separable ? go(k_dwf_single<double, true, DWF_NT>) : go(k_dwf_single<double, false, DWF_NT>);
+            return separable ? go(k_dwf_single<float, true, DWF_NT>, grants[0]) : go(k_dwf_single<float, false, DWF_NT>, grants[1]);
+        return separable ? go(k_dwf_single<double, true, DWF_NT>, grants[2]) : go(k_dwf_single<double, false, DWF_NT>, grants[3]);
     }();
     return true;
 }
@@ -620,15 +619,14 @@ bool launch_dwf_emit_stream(const DewarpFramesArgs& a, bool separable, hipStream
                     ((uintptr_t)a.range & 15) == 0 && n_items >= (stream_mode > 0 ? 1u : 4u * wgs);
     if (!ok) return false;
     const uint32_t g = std::min(n_items, wgs);
-    auto go = [&](auto kernel, uint32_t ctx_bytes) -> hipError_t {
-        const size_t lds = 2 * (size_t)ctx_bytes;
-        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3(g), dim3(576), lds, st, a, n_items);
-        return hipGetLastError();
+    static LdsGrant grants[2];   // one per k_dwf_emit_stream instantiation below
+    auto go = [&](auto kernel, uint32_t ctx_bytes, LdsGrant& grant) -> hipError_t {
+        int device = -1;   // not remembered if the runtime cannot say
+        (void)hipGetDevice(&device);
+        return launch_with_lds(kernel, dim3(g), dim3(576), 2 * (size_t)ctx_bytes, device, st, grant, a, n_items);
     };
-    *err = a.h == 128 ? go(k_dwf_emit_stream<float, 128>, dwf_stream_ctx_bytes<float, 128>())
-                      : go(k_dwf_emit_stream<float, 64>, dwf_stream_ctx_bytes<float, 64>());
+    *err = a.h == 128 ? go(k_dwf_emit_stream<float, 128>, dwf_stream_ctx_bytes<float, 128>(), grants[0])
+                      : go(k_dwf_emit_stream<float, 64>, dwf_stream_ctx_bytes<float, 64>(), grants[1]);
     return true;
 }
 

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "kernels_common.h"
+#include "launch_util.h"
 
 namespace ouster_hip_dev {
 
@@ -313,12 +314,10 @@ size_t osf_png_unfilter_lds_bytes(uint32_t w, uint32_t max_row_bytes) {
 hipError_t launch_osf_png_unfilter(const OsfUnfilterArgs& a, uint32_t n_jobs, uint32_t max_row_bytes, hipStream_t st) {
     const size_t lds = osf_png_unfilter_lds_bytes(a.w, max_row_bytes);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_osf_png_unfilter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_osf_png_unfilter, dim3(n_jobs), dim3(64), lds, st, a);
-    return hipGetLastError();
+    static LdsGrant grant;
+    int device = -1;   // not remembered if the runtime cannot say
+    if (lds > LdsGrant::FREE_BYTES) (void)hipGetDevice(&device);
+    return launch_with_lds(k_osf_png_unfilter, dim3(n_jobs), dim3(64), lds, device, st, grant, a);
 }
 
 hipError_t launch_osf_unpack(const OsfUnpackArgs& a, uint32_t n_planes, hipStream_t st) {

@@ -124,23 +124,8 @@ struct __attribute__((packed, aligned(1))) pk4 { uint32_t a; };
 struct __attribute__((packed, aligned(1))) pk8 { uint32_t a, b; };
 struct __attribute__((packed, aligned(1))) pk16 { uint32_t a, b, c, d; };
 
-#ifndef OUSTER_NT_STORES
-#define OUSTER_NT_STORES 0   // experiment switch (tools/ab/nt_variants.sh): non-temporal hint on EVERY plane / xyz store
-#endif
 #ifndef OUSTER_NT_STANDALONE
 #define OUSTER_NT_STANDALONE 1   // the hint on the stores of the standalone kernels (k_destagger / k_cartesian / k_dewarp.hip): +1.9 ... +5.7 % in-process on cold inputs
-#endif
-#ifndef OUSTER_NT_U32
-#define OUSTER_NT_U32 0      // experiment switch: the hint on the 4-byte plane stores (and whatever else asks for it)
-#endif
-#ifndef OUSTER_NT_XYZ
-#define OUSTER_NT_XYZ 0      // experiment switch: the hint on the xyz stores only
-#endif
-#ifndef OUSTER_NT_PLANES
-#define OUSTER_NT_PLANES 0   // experiment switch: the hint on the plane stores only
-#endif
-#ifndef OUSTER_NT_LOADS
-#define OUSTER_NT_LOADS 0    // experiment switch: non-temporal hint on the tile staging loads
 #endif
 // NT = non-temporal hint.  Measured in-process (BASELINE section 5): the 12 B/px profile's wide tiles gain 3 - 8 % with
 // it (128 x 32: 4.7 % in a fast region, 3 % in a slow one; 256 x 16: 7.5 %) while its 32-column k_decode loses 18 %; the
@@ -149,17 +134,14 @@ struct __attribute__((packed, aligned(1))) pk16 { uint32_t a, b, c, d; };
 typedef uint32_t u32x1_u __attribute__((aligned(1)));
 typedef uint32_t u32x2_u __attribute__((ext_vector_type(2), aligned(1)));
 typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
-#ifndef OUSTER_PLAIN_STORES
-#define OUSTER_PLAIN_STORES 0   // experiment switch: ignore every non-temporal request (the A/B partner of Spec::nt_stores)
-#endif
 template <bool NT = false>
 __device__ __forceinline__ void st4(void* p, uint32_t a) {
-    if constexpr ((NT || OUSTER_NT_STORES) && !OUSTER_PLAIN_STORES) __builtin_nontemporal_store(a, (u32x1_u*)p);
+    if constexpr (NT) __builtin_nontemporal_store(a, (u32x1_u*)p);
     else ((pk4*)p)->a = a;
 }
 template <bool NT = false>
 __device__ __forceinline__ void st8(void* p, uint32_t a, uint32_t b) {
-    if constexpr ((NT || OUSTER_NT_STORES) && !OUSTER_PLAIN_STORES) {
+    if constexpr (NT) {
         typedef uint32_t v2 __attribute__((ext_vector_type(2)));
         __builtin_nontemporal_store(v2{a, b}, (u32x2_u*)p);
     } else {
@@ -169,7 +151,7 @@ __device__ __forceinline__ void st8(void* p, uint32_t a, uint32_t b) {
 }
 template <bool NT = false>
 __device__ __forceinline__ void st16(void* p, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-    if constexpr ((NT || OUSTER_NT_STORES) && !OUSTER_PLAIN_STORES) {
+    if constexpr (NT) {
         typedef uint32_t v4 __attribute__((ext_vector_type(4)));
         __builtin_nontemporal_store(v4{a, b, c, d}, (u32x4_u*)p);
     } else {
@@ -231,7 +213,7 @@ __device__ __forceinline__ void store4v(uint8_t* p, const u32x4_t& v, uint32_t e
         case 1: st4<NT>(p, v.x | (v.y << 8) | (v.z << 16) | (v.w << 24)); break;
         case 2: st8<NT>(p, v.x | (v.y << 16), v.z | (v.w << 16)); break;
         default: {
-            if constexpr ((NT || OUSTER_NT_STORES || OUSTER_NT_U32) && !OUSTER_PLAIN_STORES) {
+            if constexpr (NT) {
                 __builtin_nontemporal_store(v, (u32x4_u*)p);
             } else {
                 struct __attribute__((packed, aligned(1))) pkv { u32x4_t v; };
@@ -437,7 +419,7 @@ __device__ __forceinline__ void store_xyz4_permuted(float* row_base, uint32_t q,
     float4* d = (float4*)row_base;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        if constexpr ((NT || OUSTER_NT_STORES) && !OUSTER_PLAIN_STORES) {
+        if constexpr (NT) {
             typedef float f4 __attribute__((ext_vector_type(4)));
             __builtin_nontemporal_store(f4{o[k][0], o[k][1], o[k][2], o[k][3]}, (f4*)(d + k * LPR + q));
         } else {
@@ -972,11 +954,7 @@ __device__ __forceinline__ const void* stage_poses(const DecodeArgs& a, uint32_t
         // at most 64 columns here (k_decode's tiles): three values per thread
         for (uint32_t i = threadIdx.x; i < ncols * 12; i += blockDim.x) {
             const uint32_t j = i / 12, k = i - j * 12, c = c0 + j;
-#ifdef OUSTER_ABLATE_POSE_LOAD   // experiment builds only: no pose is read
-            s_pose[k * ncols + j] = (XT)(k % 5 == 0);
-#else
             s_pose[k * ncols + j] = c < W ? (XT)a.xyz_poses[((size_t)f * W + c) * 16 + k] : (XT)0;
-#endif
         }
         __syncthreads();
         return s_pose;
@@ -1119,13 +1097,13 @@ __device__ __forceinline__ void decode_rows(const DecodeArgs& a, const uint32_t*
                 uint8_t* pl = (uint8_t*)a.planes[di];
                 if (pl) {
                     uint8_t* d = pl + ((size_t)f * plane_px + rowpix) * e;
-                    if (vec) store4v<NTS || OUSTER_NT_PLANES>(d, v, e);
+                    if (vec) store4v<NTS>(d, v, e);
                     else for (uint32_t c = 0; c < ncol; ++c) store1(d + c * e, v[c], e);
                 }
                 uint8_t* dp = (uint8_t*)a.destaggered[di];
                 if (dp) {
                     uint8_t* drow = dp + ((size_t)f * plane_px + (size_t)r * W) * e;
-                    if (dvec) store4v<NTS || OUSTER_NT_PLANES>(drow + (size_t)doff * e, v, e);
+                    if (dvec) store4v<NTS>(drow + (size_t)doff * e, v, e);
                     else for (uint32_t c = 0; c < ncol; ++c) {
                         uint32_t dc = doff + c; if (dc >= W) dc -= W;
                         store1(drow + (size_t)dc * e, v[c], e);
@@ -1199,12 +1177,7 @@ __device__ __forceinline__ void decode_rows(const DecodeArgs& a, const uint32_t*
                     const double rm = (double)rr - lut.n;
 #pragma unroll
                     for (int k = 0; k < 3; ++k) {
-#ifdef OUSTER_ABLATE_XYZ_MATH   // experiment builds only (tools/ab/ablate.sh): how much of the kernel's time is the arithmetic?
-                        const XT t = (XT)rr;
-                        (void)rm;
-#else
                         const XT t = (XT)fma(rm, d[c][k], cc.kc[c][k]);
-#endif
                         p[c][k] = rr ? t : (XT)0;
                     }
                 }
@@ -1217,12 +1190,6 @@ __device__ __forceinline__ void decode_rows(const DecodeArgs& a, const uint32_t*
                             if constexpr (POSE_REGS) m[k][c] = m_pose[k][c];
                             else m[k][c] = ((const XT*)s_pose)[(size_t)k * (QPR * 4) + jq + c];
                         }
-#ifdef OUSTER_ABLATE_POSE_MATH   // experiment builds only: the table stays in registers, the arithmetic goes
-#pragma unroll
-                    for (int k = 0; k < 12; ++k)
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) asm volatile("" ::"v"(m[k][c]));
-#else
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const XT x = p[c][0], y = p[c][1], z = p[c][2];
@@ -1230,13 +1197,12 @@ __device__ __forceinline__ void decode_rows(const DecodeArgs& a, const uint32_t*
                         p[c][1] = m[4][c] * x + m[5][c] * y + m[6][c] * z + m[7][c];
                         p[c][2] = m[8][c] * x + m[9][c] * y + m[10][c] * z + m[11][c];
                     }
-#endif
                 }
                 XT* dst = out + ((size_t)f * plane_px + rowpix) * 3;
                 if constexpr (XYZM == 1) {
                     if (VECONLY || (a.vec_ok && seg0 + 4 * LPR <= W)) {  // my wave's whole row segment exists
 #if OUSTER_XYZ_PERMUTE
-                        store_xyz4_permuted<LPR, NTX || OUSTER_NT_XYZ>(dst - (size_t)(4 * ql) * 3, ql, p);
+                        store_xyz4_permuted<LPR, NTX>(dst - (size_t)(4 * ql) * 3, ql, p);
 #else
                         store_xyz4_coalesced<LPR>(s_xyz, tid, dst - (size_t)(4 * ql) * 3, ql, p);
 #endif

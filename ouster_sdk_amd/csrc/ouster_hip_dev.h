@@ -90,7 +90,7 @@ struct DecodeArgs {
     uint32_t pose_lds_off;    // byte offset of the tile's pose table in dynamic LDS (set by the launchers)
     uint32_t crew_lds_off;    // byte offset of the crew's bookkeeping (CrewLds) in dynamic LDS (set by the launchers)
 #ifdef OUSTER_PHASE_TIMING
-    uint64_t* phase_times;   // experiment builds only (tools/ab/phase_timing.sh): [workgroup][8] s_memtime stamps of k_decode_wide
+    uint64_t* phase_times;   // experiment builds only (tools/ab/phase_timing.py): [workgroup][8] s_memtime stamps of k_decode_wide
 #endif
 };
 

@@ -118,7 +118,7 @@ __device__ __forceinline__ void wide_tile(const DecodeArgs& a, uint32_t* smem, u
     // timestamp) words of its columns, the destagger offsets and the per-beam table rows -- is put in
     // flight BEHIND the tile's loads (issue_small, called from the staging loop) and used after the tile
     // has been written to LDS: a consumer right behind one of these loads would cost the workgroup a
-    // full memory latency before its tile is even requested (18 % of its life, tools/ab/phase_timing.sh).
+    // full memory latency before its tile is even requested (18 % of its life, tools/ab/phase_timing.py).
     RawWin w_mid[NJ], w_st[NJ], w_ts[NJ], w_alert[NJ];
     uint64_t pk_ts[NJ];
     constexpr int NBT = 3;   // at most 84 rows per tile (setup_wide): three table doubles per thread
@@ -169,13 +169,8 @@ __device__ __forceinline__ void wide_tile(const DecodeArgs& a, uint32_t* smem, u
 #pragma unroll
                 for (int k = 0; k < NPOSE; ++k) {
                     const uint32_t i = tid + (uint32_t)k * NT, j = i / 6u, kk = (i - j * 6u) * 2u;
-#ifdef OUSTER_ABLATE_POSE_LOAD   // experiment builds only: no pose is read
-                    r_pose[k] = double2{kk == 0 ? 1.0 : 0.0, 0.0};
-                    (void)j;
-#else
                     r_pose[k] = (i < (uint32_t)TW * 6u && c0 + j < W)
                                     ? *(const double2*)(a.xyz_poses + ((size_t)f * W + c0 + j) * 16 + kk) : double2{0.0, 0.0};
-#endif
                 }
             }
         }
@@ -222,11 +217,7 @@ __device__ __forceinline__ void wide_tile(const DecodeArgs& a, uint32_t* smem, u
                 const bool tail = q > lim;
                 const uint8_t* qs = ok ? (tail ? lim : q) : fbase;
                 const int32_t shift = tail ? (int32_t)((q - lim) >> 2) : 0;
-#if OUSTER_NT_LOADS
-                t[k] = __builtin_nontemporal_load((const u32x4*)qs);
-#else
                 t[k] = *(const u32x4*)qs;
-#endif
                 pj[k] = ok ? ((j << 16) | (uint32_t)(((int32_t)(ch * 4u) - (int32_t)(delta >> 2) - shift) & 0xffff)) : 0x8000u;
                 j += dj; ch += dc;
                 if (ch >= NCH) { ch -= NCH; ++j; }
@@ -271,9 +262,6 @@ __device__ __forceinline__ void wide_tile(const DecodeArgs& a, uint32_t* smem, u
                 }
             }
             s_pose = sp;
-#ifdef OUSTER_ABLATE_POSE_ALL   // experiment builds only: the POSES instantiation runs, its pose code does not
-            s_pose = nullptr;
-#endif
         }
     }
     if (!mapped && rc == 0 && tile == 0 && tid == 0 && a.frame_meta) a.frame_meta[f] = frame_meta_first_present(a.g, fbase, a.packet_stride, count);
@@ -417,7 +405,7 @@ __device__ __forceinline__ void sum_valid_columns(const DecodeArgs& a, uint64_t 
 // call's starts at zero (zeroed by the call before), the other is zeroed for the next call; the ready words ([ready_off + f],
 // the buffer's second half) carry the tag and are never cleared.
 // ------------------------------------------------------------------------------------
-#ifdef OUSTER_PHASE_TIMING   // experiment builds (tools/ab/phase_timing.sh): per workgroup 64 words: [0] start, [1] events, then 4 per ticket
+#ifdef OUSTER_PHASE_TIMING   // experiment builds (tools/ab/phase_timing.py): per workgroup 64 words: [0] start, [1] events, then 4 per ticket
 #define FSTAMP_BEGIN() uint64_t fs0_ = PT_NOW(), fs1_ = 0
 #define FSTAMP_MID() do { fs1_ = PT_NOW(); } while (0)
 #define FSTAMP_END(kind, n) do { if (a.phase_times && tid == 0) { uint64_t* q_ = a.phase_times + (size_t)blockIdx.x * 64; const uint64_t e_ = q_[1]; \

@@ -6,8 +6,9 @@ import os
 import cpp_tools
 
 BATCH_TOOLS = ["image_batch_tool", "frame_ops_batch_tool", "pose_batch_tool", "normals_batch_tool", "voxel_batch_tool", "icp_batch_tool"]
-SNIPPETS = ["image_processing_snippet", "frame_ops_snippet", "pose_snippet", "normals_snippet", "voxel_snippet", "icp_snippet"]
-LANES = ["normals_lanes", "voxel_lanes", "icp_lanes"]
+SNIPPETS = ["image_processing_snippet", "frame_ops_snippet", "pose_snippet", "normals_snippet", "voxel_snippet", "icp_snippet", "tonemap_snippet",
+            "tonemap_eigen_snippet"]
+LANES = ["normals_lanes", "voxel_lanes", "icp_lanes", "tonemap_lanes"]
 
 
 def test_every_program_builds():

@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-import tonemap_tools
+import cpp_tools
 import tonemap_cases as K
 import tonemap_model as M
 from conftest import ROOT, has_gpu
@@ -131,15 +131,15 @@ def test_update_without_a_gpu_raises_and_leaves_the_image(dtype):
 
 
 def test_cpp_caller_compiles_links_and_runs():
-    """tests/cpp/tonemap_snippet.cpp, built by tests/cpp/tonemap.mk with the flags tests/cpp/Makefile gives the other snippets, -Werror among them"""
-    p = tonemap_tools.run("tonemap_snippet", [], timeout=300)
+    """tests/cpp/tonemap_snippet.cpp, built by tests/cpp/Makefile with the flags of the other snippets, -Werror among them"""
+    p = cpp_tools.run("tonemap_snippet", [], timeout=300)
     assert p.stdout.startswith("ok" if has_gpu() else "no-gpu"), p.stdout
 
 
 def test_eigen_tensor_maps_bind_where_the_mirror_takes_rgb_img_ref():
     """tests/cpp/tonemap_eigen_snippet.cpp with -DOUSTER_HIP_USE_EIGEN over the mocked Tensor module: temporaries of
     Eigen::TensorMap<rgb_img_t<T>>, const and not, in the reference's own call spelling"""
-    assert tonemap_tools.run("tonemap_eigen_snippet", [], timeout=300).stdout.strip() == "ok"
+    assert cpp_tools.run("tonemap_eigen_snippet", [], timeout=300).stdout.strip() == "ok"
 
 
 def steps(tmp_path, kind, model, calls):
@@ -150,7 +150,7 @@ def steps(tmp_path, kind, model, calls):
                             model.lo_percentile, model.hi_percentile, model.damping, getattr(model, "compress_dr_max_lum", 0.0)))
         for (n, lo, hi), flag in calls:
             f.write(struct.pack("<2I2d", n, int(flag), lo, hi))
-    tonemap_tools.run("tonemap_snippet", ["steps", src, dst])
+    cpp_tools.run("tonemap_snippet", ["steps", src, dst])
     raw = open(dst, "rb").read()
     size = (48 if kind == 0 else 32) + 16
     assert len(raw) == size * len(calls)

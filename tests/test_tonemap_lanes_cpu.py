@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-import tonemap_tools
+import cpp_tools
 import tonemap_cases as K
 import tonemap_model as M
 
@@ -20,7 +20,7 @@ GUARD = -7.25
 
 @pytest.fixture(scope="module")
 def lanes():
-    return tonemap_tools.build("tonemap_lanes")[0]
+    return cpp_tools.build("tonemap_lanes")[0]
 
 
 def run(exe, tmp_path, images, records, out_dtype, in_place, pad_in=0, pad_out=0, pieces=0):
