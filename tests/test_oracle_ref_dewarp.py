@@ -62,19 +62,27 @@ def test_oracle_equals_the_compiled_reference(oracle, T, rtol):
     h, w = 32, 128
     cal = O.synthetic_calib(h=h, w=w, cpp=16)
     d, o = cal.xyz_lut(False)
-    for trial in range(4):
+    for trial in range(5):
         r = g.integers(0, 200000, (h, w)).astype(np.uint32)
         r[g.random(r.shape) < 0.3] = 0
         st = (g.random(w) < 0.8).astype(np.uint32) * g.integers(1, 4, w).astype(np.uint32)
         if trial == 3:
             st[:] = 0
+        if trial == 4:
+            # non-zero status with bit 0 clear on columns before the first and after the last valid one, nothing else outside
+            # the span: by construction, not by the draw.  Their ranges pass the gate, so emitting them would show.
+            st[:10] = 0; st[100:] = 0; st[10] = 1; st[99] = 3
+            st[[7, 8, 101, 102]] = 2
+            r[0, [7, 8, 101, 102]] = 5000
         ts = g.integers(0, 1 << 60, w).astype(np.uint64)
         poses = g.normal(size=(w, 4, 4))
         poses[:, 3] = [0, 0, 0, 1]
-        lo, hi = (0.0, 1000.0) if trial == 0 else (0.5 + trial, 60.0 * trial)
+        lo, hi = (0.0, 1000.0) if trial == 0 else (1.0, 60.0) if trial == 4 else (0.5 + trial, 60.0 * trial)
         a = O.dewarp_frame(r, st, ts, poses, d.astype(T), o.astype(T), lo, hi)
         b = dewarp_ref.dewarp_frame(r, st, ts, poses, d.astype(T), o.astype(T), lo, hi)
         assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]), trial
+        if trial == 4:
+            assert b[1].min() == 10 and b[1].max() == 99 and len(b[1]) > 100 and not set(b[1].tolist()) & {7, 8, 101, 102}
         if len(b[0]):
             assert np.abs(a[0].astype(np.float64) - b[0].astype(np.float64)).max() <= rtol * np.abs(b[0]).max() * 4
         else:
