@@ -38,6 +38,9 @@ const KnobDef knob_table[] = {
     {"slotmap", "OUSTER_HIP_SLOTMAP", &Knobs::slotmap},
     {"dwf_stream", "OUSTER_HIP_DWF_STREAM", &Knobs::dwf_stream},   // the frame dewarp's emit kernel: -1 auto | 0 k_dwf_emit | 1 the persistent k_dwf_emit_stream where eligible
     {"stream_loader", "OUSTER_HIP_STREAM_LOADER", &Knobs::stream_loader},   // loader waves of k_decode_stream2 (0 = k_decode_stream: every wave fetches)
+    // tile contexts of k_decode_stream2's ring, 2 .. 6: the loaders fetch that many tiles less one ahead (A/B).  0 = the plan's choice;
+    // a depth that does not fit in LDS, or in the loaders' vmcnt, at any tile height is refused (the launch takes another kernel)
+    {"stream_slots", "OUSTER_HIP_STREAM_SLOTS", &Knobs::stream_slots},
     {"pose_direct", "OUSTER_HIP_POSE_DIRECT", &Knobs::pose_direct},   // 1 = k_pose_interp stores each lane's own row (128 B lane stride) instead of going through LDS (A/B)
     {"tonemap_bands", "OUSTER_HIP_TONEMAP_BANDS", &Knobs::tonemap_bands},   // k_tm_hist: workgroups (bands of rows) per tile, 1 .. 64; 0 = the launch's own choice (A/B)
 };
@@ -74,6 +77,12 @@ size_t slotmap_lds_bytes(uint32_t W, uint32_t cpp, uint32_t slots_per_frame) {
 
 // ---- the pieces ----------------------------------------------------------------------------------------------------------
 namespace {
+
+// Does plan_stream give the 12 B/px static profiles a ring deeper than two on its own?  No: measured (profiles/r07_ring,
+// DESIGN.md 3.2e), the decoders' wait at the tile barrier is not a wait for the fetch -- at 128 x 16 it is the same 12 % of the
+// tile period with 2, 3 and 5 slots -- and the only heights that leave room for a third slot (128 x 16, 256 x 8) cost 7 - 12 %
+// against the tall tile.  The rule below stays for the day a taller tile fits more than twice; stream_slots forces a depth.
+constexpr bool STREAM_RING_DEFAULT = false;
 
 // optimistic pass + fix-up pass when the buffer has one slot per column of the frame; everything through the general
 // mapping otherwise
@@ -238,8 +247,26 @@ std::optional<StreamPlan> plan_stream(const PlanInput& in, int tw) {
         !plan_field(g.col_timestamp, sa.hdr_dw, sa.n_hdr, 8, sa.ts) ||
         !plan_field(g.alert_flags, sa.pkt_dw, sa.n_pkt, 4, sa.alert))
         return std::nullopt;
-    auto fits = [&](uint32_t tr) -> bool {
+    // the loader-wave form (k_decode_stream2), the only one with a ring deeper than two
+    sa.loader = (kn.stream_loader > 0 && (tw == 128 || tw == 256) && !in.gate_counts && kn.stream_order == 0)
+                    ? (uint32_t)std::min(kn.stream_loader, 4) : 0u;
+    // LDS-DMA instructions loader wave l issues per tile, in the kernel's own order: pixel instruction k belongs to wave
+    // k % loader, and so does the k-th instruction of the small tables
+    auto count_dma = [&]() {
+        const uint32_t small = sa.n_hdr * ((uint32_t)tw / 64u) + sa.n_pkt + (in.host_ts ? 2u : 0u) +
+                               (in.destagger_mask ? (sa.tr + 63u) / 64u : 0u) +
+                               ((in.xyzm == 1 || in.xyzm == 2) ? (sa.tr * 18u + 63u) / 64u : 0u);
+        uint32_t most = 0;
+        for (uint32_t l = 0; l < 4; ++l) {
+            auto share = [&](uint32_t n) { return (l < sa.loader && n > l) ? (n - l + sa.loader - 1) / sa.loader : 0u; };
+            sa.dma_per_tile[l] = share(sa.npix_instr) + share(small);
+            most = std::max(most, sa.dma_per_tile[l]);
+        }
+        return most;
+    };
+    auto fits = [&](uint32_t tr, uint32_t nslot) -> bool {
         if (tr == 0 || tr % rpp || H % tr || (tr * chan) % 16) return false;
+        if (nslot < 2 || nslot > (sa.loader ? STREAM_MAX_SLOTS : 2u)) return false;
         sa.tr = tr;
         sa.nch = H / tr;
         sa.ncell = tr * chan / 16 + 1;
@@ -251,15 +278,43 @@ std::optional<StreamPlan> plan_stream(const PlanInput& in, int tw) {
         sa.off_off = o; o += ((tr + 63) / 64) * 256u;
         sa.beam_off = o; o += ((tr * 18u + 63) / 64) * 256u;
         sa.ctx_bytes = (o + 1023u) & ~1023u;
-        sa.fixed_off = 2u * sa.ctx_bytes;
+        sa.nslot = nslot;
+        sa.fixed_off = nslot * sa.ctx_bytes;
         sa.lds_bytes = sa.fixed_off + 3u * (uint32_t)tw * 4u + 32u;
-        return sa.lds_bytes <= 160u * 1024u;
+        if (sa.lds_bytes > 160u * 1024u) return false;
+        // a loader waits for tile i behind nslot - 2 newer tiles of its own: that many instructions must fit in vmcnt
+        return (nslot - 2u) * count_dma() <= STREAM_MAX_VMCNT;
     };
-    bool ok = false;
-    if (kn.stream_rows > 0) ok = fits((uint32_t)kn.stream_rows);
-    else
-        for (uint32_t tr = H / rpp * rpp; tr >= rpp && !ok; tr -= rpp) ok = fits(tr);   // the tallest tile that fits twice
-    if (!ok) return std::nullopt;
+    // How deep, how tall.  A forced depth (knob stream_slots: A/B, tests) is taken as it is or refused, never clamped.
+    // Left to the plan, every profile keeps the tallest tile that fits twice.  With STREAM_RING_DEFAULT set the 12 B/px
+    // profiles (the shortest-lived tiles) would take, among the heights that fit twice, the one whose ring keeps the most
+    // packet bytes in flight, (nslot - 1) * ctx_bytes, the taller on a tie, and no tile of fewer than two passes of the
+    // workgroup.
+    const uint32_t forced_slots = kn.stream_slots > 0 ? (uint32_t)kn.stream_slots : 0u;
+    const uint32_t max_slots = sa.loader ? STREAM_MAX_SLOTS : 2u;
+    const bool ring = STREAM_RING_DEFAULT && sa.loader && (in.spec == SPEC_SINGLE || in.spec == SPEC_LEGACY);
+    auto deepest = [&](uint32_t tr) -> uint32_t {   // of the ring at this height (0: none); leaves sa at that plan
+        if (forced_slots) return fits(tr, forced_slots) ? forced_slots : 0u;
+        if (!fits(tr, 2u)) return 0u;
+        for (uint32_t n = ring ? max_slots : 2u; n > 2; --n)
+            if (fits(tr, n)) return n;
+        return fits(tr, 2u) ? 2u : 0u;
+    };
+    uint32_t best_tr = 0, best_n = 0;
+    if (kn.stream_rows > 0) {
+        best_tr = (uint32_t)kn.stream_rows;
+        best_n = deepest(best_tr);
+    } else {
+        uint32_t best_fly = 0;
+        for (uint32_t tr = H / rpp * rpp; tr >= rpp; tr -= rpp) {
+            const uint32_t n = deepest(tr);
+            if (!n) continue;
+            const uint32_t fly = (n - 1u) * sa.ctx_bytes;
+            if (!best_n || (ring && !forced_slots && tr >= 2u * rpp && fly > best_fly)) { best_tr = tr; best_n = n; best_fly = fly; }
+            if (!ring || forced_slots) break;   // the tallest tile that fits
+        }
+    }
+    if (!best_n || !fits(best_tr, best_n)) return std::nullopt;
     if (in.gate_counts && sa.nch > OUSTER_HIP_GATE_CHUNKS) return std::nullopt;
     sa.groups = per_xcd / ct;
     const uint64_t tiles = (uint64_t)in.n_frames * ct * sa.nch, wgs = 8ull * ct * sa.groups;
@@ -271,8 +326,6 @@ std::optional<StreamPlan> plan_stream(const PlanInput& in, int tw) {
     const uint32_t stores_per_wave = streams * (sa.tr / rpp);
     sa.wait0 = (kn.stream_wait == 0 && stores_per_wave >= 64) ? 0u : 1u;
     sa.order = (uint32_t)kn.stream_order;
-    sa.loader = (kn.stream_loader > 0 && (tw == 128 || tw == 256) && !in.gate_counts && kn.stream_order == 0)
-                    ? (uint32_t)std::min(kn.stream_loader, 4) : 0u;
     p.shape = TileShape{sa.tr, sa.nch, 0u, ct, 0u};
     return p;
 }
@@ -335,6 +388,11 @@ uint64_t tuner_key(const PlanInput& in, const Candidates& c) {
     mix(in.plane_mask); mix(in.destagger_mask);
     mix((in.xyz_mask & 3u) | (in.gate_counts ? 4u : 0u) | (in.xyz_poses ? 8u : 0u));
     mix((uint64_t)c.stream_auto); mix((uint64_t)c.stream_alt);
+    // the ring depth of the persistent candidates: a verdict timed on another depth is not this kernel's
+    for (int tw : {c.stream_auto, c.stream_alt})
+        if (tw)
+            if (const auto s = plan_stream(in, tw))
+                if (s->sa.nslot != 2) mix(0x100u + s->sa.nslot);
     return key;
 }
 

@@ -49,7 +49,7 @@ constexpr uint32_t FS_SEQ = 0, FS_TAG = 1, FS_TICKET = 2, FS_ANY = 20, FS_WORDS 
 
 constexpr size_t XYZ_SCRATCH_BYTES = OUSTER_XYZ_PERMUTE ? 0 : 4 * 192 * 16;
 
-// k_decode_stream (persistent, double-buffered tiles filled by LDS-DMA): what the host works out
+// k_decode_stream (persistent, a ring of tile contexts filled by LDS-DMA): what the host works out
 // once per launch.  A tile context in LDS = the pixel image (TW column blocks of `ncell` 16 B cells, block of column j at
 // index j/4 + (TW/4)*(j%4)), then the column-header dwords [n_hdr][TW], the packet-level dwords [n_pkt + 2][64], the
 // destagger offsets of the tile's rows and their per-beam xyz constants.
@@ -62,7 +62,7 @@ struct StreamArgs {
     uint32_t ncell;            // 16 B cells per column block (the piece of tr rows plus its 16 B phase)
     uint32_t npix_instr;       // 1 KB wave-instructions that fill the pixel image
     uint32_t hdr_off, pkt_off, off_off, beam_off, ctx_bytes;  // byte offsets inside a tile context / its size
-    uint32_t fixed_off;        // byte offset of the per-workgroup tables behind the two contexts
+    uint32_t fixed_off;        // byte offset of the per-workgroup tables behind the contexts (nslot * ctx_bytes)
     uint32_t n_hdr, n_pkt;     // dwords fetched per column / per packet
     uint32_t hdr_dw[8];        //   their dword offsets from the column start
     uint32_t pkt_dw[4];        //   ... from the packet start
@@ -72,7 +72,13 @@ struct StreamArgs {
     uint32_t lds_bytes;
     uint32_t order;            // how a group walks the XCD's (frame, row chunk) items, see the kernel
     uint32_t loader;           // > 0: k_decode_stream2 with that many loader waves behind the eight decoding ones (1..4)
+    uint32_t nslot;            // tile contexts in LDS (2: double-buffered; k_decode_stream2 takes up to STREAM_MAX_SLOTS and fetches nslot - 1 tiles ahead)
+    uint32_t dma_per_tile[4];  // k_decode_stream2: LDS-DMA instructions loader wave l issues per tile (what its vmcnt waits count in)
 };
+constexpr uint32_t STREAM_MAX_SLOTS = 6;
+// k_decode_stream2's loader waves wait for "tile i has landed" with s_waitcnt vmcnt(k), k = the DMA instructions the wave has issued
+// for newer tiles: their queue holds nothing else and retires in order.  The counter has 6 bits.
+constexpr uint32_t STREAM_MAX_VMCNT = 63;
 
 // ---- LDS sizes ---------------------------------------------------------------------------------------------------------
 // resolve_frame's scratch (kernels_common.h), in words
@@ -93,7 +99,7 @@ struct Knobs {
     int tile = 0, wide = -1, wide_kb = 64, wide_rows = 0, wide_min_blocks = 512, tune = 1, xcd = 1, fast = 1;
     int dewarp_single_pass = 0, beam_lds = 1, fixup = 1, small = 1, fixup_rows = 0, hdr_words = 1, fixup_wide = 1;
     int stream = -1, stream_rows = 0, stream_wait = 1, stream_min_tiles = 8, stream_order = 0, slotmap = 1;
-    int dwf_stream = -1, stream_loader = 4;
+    int dwf_stream = -1, stream_loader = 4, stream_slots = 0;
     int pose_direct = 0;
     int tonemap_bands = 0;
 };
@@ -119,6 +125,7 @@ struct PlanInput {
     uint64_t plane_mask, destagger_mask; // bit i: planes[i] / destaggered[i] requested
     uint32_t xyz_mask;                   // bit k: xyz[k] requested
     bool gate_counts;
+    bool host_ts;                        // host timestamps are handed in and packet_timestamp is requested (two more dwords per tile)
     uint32_t cus, resident_wgs;
     bool may_resolve;                    // the build has k_decode_wide_resolved (OUSTER_EXPERIMENTS)
 };

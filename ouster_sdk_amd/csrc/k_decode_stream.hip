@@ -77,6 +77,23 @@ __device__ __forceinline__ const __attribute__((address_space(4))) T* as_const(c
     return (const __attribute__((address_space(4))) T*)(uintptr_t)p;
 }
 
+// s_waitcnt vmcnt(k) for a wave-uniform k: the count is an immediate, so one statement per value (a loader wave of
+// k_decode_stream2 waits on a handful of them: tiles requested behind the one it needs x its instructions per tile).
+// A k past the 6-bit counter waits for everything.
+__device__ __forceinline__ void wait_vmcnt_le(uint32_t k) {
+#define OUSTER_VMW1(n) case n: asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory"); break;
+#define OUSTER_VMW8(a, b, c, d, e, f, g, h) OUSTER_VMW1(a) OUSTER_VMW1(b) OUSTER_VMW1(c) OUSTER_VMW1(d) OUSTER_VMW1(e) OUSTER_VMW1(f) OUSTER_VMW1(g) OUSTER_VMW1(h)
+    switch (k) {
+        OUSTER_VMW8(1, 2, 3, 4, 5, 6, 7, 8) OUSTER_VMW8(9, 10, 11, 12, 13, 14, 15, 16) OUSTER_VMW8(17, 18, 19, 20, 21, 22, 23, 24)
+        OUSTER_VMW8(25, 26, 27, 28, 29, 30, 31, 32) OUSTER_VMW8(33, 34, 35, 36, 37, 38, 39, 40) OUSTER_VMW8(41, 42, 43, 44, 45, 46, 47, 48)
+        OUSTER_VMW8(49, 50, 51, 52, 53, 54, 55, 56) OUSTER_VMW1(57) OUSTER_VMW1(58) OUSTER_VMW1(59) OUSTER_VMW1(60) OUSTER_VMW1(61)
+        OUSTER_VMW1(62) OUSTER_VMW1(63)
+        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    }
+#undef OUSTER_VMW8
+#undef OUSTER_VMW1
+}
+
 // field value from the fetched header dwords of column / packet `j` (slot-major table, `n` entries per slot)
 __device__ __forceinline__ uint64_t plan_field(const uint32_t* tab, uint32_t n, uint32_t j, const FieldPlan& p,
                                                const ouster_hip_bits& b) {
@@ -342,10 +359,53 @@ __global__ __launch_bounds__(512) void k_decode_stream(DecodeArgs a, StreamArgs 
 // issue order, so until those (slow: they queue behind the whole chip's stores) reads have landed, the 6-bit counter has
 // only 63 - 12 slots left for the wave's stores, and in a slow buffer placement -- where stores want MORE of them in
 // flight -- the kernel lost 4 - 10 % against k_decode_wide (tools/ab/lottery_variants.py).  Here the decoding waves issue
-// nothing but stores.  One workgroup barrier per tile: the loader reaches it when tile i+1 has landed, the decoders
+// nothing but stores.  One workgroup barrier per tile: a loader reaches barrier i when tile i has landed, the decoders
 // when they are done with tile i-1's context; every lane classifies its own four columns from the fetched header
 // words (no shared validity table, hence no second barrier), invalid columns are zeroed per pixel.
+// The contexts form a RING of sp.nslot (2 .. 6), tile t in slot t % nslot, and the loaders run nslot - 1 tiles ahead:
+// behind barrier i the decoders have left tile i-1's slot, which is the slot of tile i + nslot - 1, and that tile is
+// requested.  A loader's vmcnt queue holds its LDS-DMA instructions and nothing else, and they retire in order, so
+// "tile i has landed" is vmcnt <= (tiles it has requested behind i) x (its instructions per tile, sp.dma_per_tile):
+// no flag, no spin.  nslot = 2 is the double-buffered kernel as it always was.
 // ------------------------------------------------------------------------------------
+// Experiment builds (-DOUSTER_PHASE_TIMING, tools/ab/phase_timing.py ring): 16 words per workgroup, cycle-counter ticks.
+//   thread 0 (a decoding wave):  [0] start  [1] end  [2] sum and [5] max of its wait at the top-of-tile barrier over tiles 1..,
+//                                [3] the same wait for tile 0  [4] tiles  [6] ring depth  [7] XCC
+//   lane 0 of loader 0:          [8] sum, [9] max, [10] min of (tile seen landed - tile requested), [11] sum of its own wait
+//                                for the landing, [12] tiles
+#ifdef OUSTER_PHASE_TIMING
+#define PHASE2_NOW() __builtin_readcyclecounter()
+#define PHASE2_DECODER_BEGIN() \
+    uint64_t* const pt2_ = a.phase_times ? a.phase_times + (size_t)blockIdx.x * 16 : nullptr; \
+    const uint64_t pt2_start = PHASE2_NOW(); uint64_t pt2_w0 = 0, pt2_sum = 0, pt2_max = 0, pt2_first = 0
+#define PHASE2_DECODER_WAIT0() pt2_w0 = PHASE2_NOW()
+#define PHASE2_DECODER_WAIT1() do { const uint64_t d_ = PHASE2_NOW() - pt2_w0; if (it == 0) pt2_first = d_; else { pt2_sum += d_; pt2_max = d_ > pt2_max ? d_ : pt2_max; } } while (0)
+#define PHASE2_DECODER_END() do { if (pt2_ && tid == 0) { uint32_t xcc_; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_)); \
+    pt2_[0] = pt2_start; pt2_[1] = PHASE2_NOW(); pt2_[2] = pt2_sum; pt2_[3] = pt2_first; pt2_[4] = n_mine; pt2_[5] = pt2_max; pt2_[6] = sp.nslot; pt2_[7] = xcc_; } } while (0)
+#define PHASE2_LOADER_BEGIN() \
+    uint64_t* const pl2_ = a.phase_times ? a.phase_times + (size_t)blockIdx.x * 16 : nullptr; \
+    uint64_t pl2_iss[STREAM_MAX_SLOTS], pl2_w0 = 0, pl2_sum = 0, pl2_max = 0, pl2_min = ~0ull, pl2_stall = 0; uint32_t pl2_slot = 0; \
+    _Pragma("unroll") for (uint32_t j_ = 0; j_ < STREAM_MAX_SLOTS; ++j_) pl2_iss[j_] = PHASE2_NOW()
+#define PHASE2_LOADER_WAIT0() pl2_w0 = PHASE2_NOW()
+#define PHASE2_LOADER_WAIT1() do { const uint64_t t_ = PHASE2_NOW(); uint64_t i_ = 0; \
+    _Pragma("unroll") for (uint32_t j_ = 0; j_ < STREAM_MAX_SLOTS; ++j_) if (j_ == pl2_slot) i_ = pl2_iss[j_]; \
+    const uint64_t d_ = t_ - i_; pl2_sum += d_; pl2_max = d_ > pl2_max ? d_ : pl2_max; pl2_min = d_ < pl2_min ? d_ : pl2_min; pl2_stall += t_ - pl2_w0; \
+    pl2_slot = pl2_slot + 1u == nslot ? 0u : pl2_slot + 1u; } while (0)
+#define PHASE2_LOADER_ISSUE() do { const uint64_t t_ = PHASE2_NOW(); \
+    _Pragma("unroll") for (uint32_t j_ = 0; j_ < STREAM_MAX_SLOTS; ++j_) if (j_ == slot) pl2_iss[j_] = t_; } while (0)
+#define PHASE2_LOADER_END() do { if (pl2_ && li == 0 && lane == 0) { pl2_[8] = pl2_sum; pl2_[9] = pl2_max; pl2_[10] = pl2_min; pl2_[11] = pl2_stall; pl2_[12] = n_mine; } } while (0)
+#else
+#define PHASE2_DECODER_BEGIN() do {} while (0)
+#define PHASE2_DECODER_WAIT0() do {} while (0)
+#define PHASE2_DECODER_WAIT1() do {} while (0)
+#define PHASE2_DECODER_END() do {} while (0)
+#define PHASE2_LOADER_BEGIN() do {} while (0)
+#define PHASE2_LOADER_WAIT0() do {} while (0)
+#define PHASE2_LOADER_WAIT1() do {} while (0)
+#define PHASE2_LOADER_ISSUE() do {} while (0)
+#define PHASE2_LOADER_END() do {} while (0)
+#endif
+
 template <class S, int TW, int XYZM>
 __global__ __launch_bounds__(768) void k_decode_stream2(DecodeArgs a, StreamArgs sp) {
     constexpr int NT = 512, QPR = TW / 4;          // decoding threads; thread 512.. = the loader wave
@@ -443,13 +503,27 @@ __global__ __launch_bounds__(768) void k_decode_stream2(DecodeArgs a, StreamArgs
                     if (mine()) glds4(bt + (i < nb ? i : nb - 1u), ldsb + sp.beam_off + k * 256u);
                 }
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // landed (only this wave's queue: it holds nothing else)
         };
-        fetch(item(0), 0);
+        // tiles 0 .. issued-1 are requested; `it` is waited for behind the issued-1-it newer ones (fewer at either end of a
+        // short list: nothing is requested for tiles that do not exist)
+        const uint32_t nslot = sp.nslot, per_tile = sp.dma_per_tile[li];
+        uint32_t issued = 0, slot = 0;
+        PHASE2_LOADER_BEGIN();
+        for (; issued < n_mine && issued + 1u < nslot; ++issued) fetch(item(issued), issued);
+        slot = issued;
         for (uint32_t it = 0; it < n_mine; ++it) {
-            __syncthreads();   // tile `it` is in its context; the other context is free (the decoders are done with tile it-1)
-            if (it + 1 < n_mine) fetch(item(it + 1), (it + 1) & 1u);
+            PHASE2_LOADER_WAIT0();
+            wait_vmcnt_le((issued - 1u - it) * per_tile);
+            PHASE2_LOADER_WAIT1();
+            __syncthreads();   // tile `it` is in its slot; the decoders are done with tile it-1, whose slot tile it+nslot-1 takes
+            if (issued < n_mine) {
+                PHASE2_LOADER_ISSUE();
+                fetch(item(issued), slot);
+                ++issued;
+                slot = slot + 1u == nslot ? 0u : slot + 1u;
+            }
         }
+        PHASE2_LOADER_END();
         return;
     }
 
@@ -469,8 +543,9 @@ __global__ __launch_bounds__(768) void k_decode_stream2(DecodeArgs a, StreamArgs
     uint32_t cur_lut = 0xffffffffu;
     const bool hdr_lane = tid < (uint32_t)QPR;   // the lanes that write the column headers / packet-level outputs (first row of wave 0)
 
-    for (uint32_t it = 0; it < n_mine; ++it) {
-        const uint32_t b = it & 1u, s = item(it);
+    PHASE2_DECODER_BEGIN();
+    for (uint32_t it = 0, b = 0; it < n_mine; ++it, b = b + 1u == sp.nslot ? 0u : b + 1u) {   // b: tile it's slot of the ring
+        const uint32_t s = item(it);
         const uint32_t m = s / nch, rc = s - m * nch, f = xcd + 8u * m;
         const uint32_t r0 = rc * TR;
         uint32_t count = a.slots_per_frame;
@@ -487,7 +562,9 @@ __global__ __launch_bounds__(768) void k_decode_stream2(DecodeArgs a, StreamArgs
                 load_colconst(cc, lut, c0 + q * 4u, W);
             }
         }
+        PHASE2_DECODER_WAIT0();
         __syncthreads();
+        PHASE2_DECODER_WAIT1();
 
         const uint32_t* s_pix = (const uint32_t*)((const uint8_t*)smem + b * sp.ctx_bytes);
         const uint32_t* s_hdr = s_pix + (sp.hdr_off >> 2);
@@ -558,6 +635,7 @@ __global__ __launch_bounds__(768) void k_decode_stream2(DecodeArgs a, StreamArgs
             a, s_pix, pxd, cc, s_off, nullptr, (XYZM == 1 || XYZM == 2) ? s_beam : nullptr, nullptr, lut, f, c0, r0, TR, vq,
             rc, nch, nullptr);
     }
+    PHASE2_DECODER_END();
 }
 
 // ------------------------------------------------------------------------------------
@@ -586,6 +664,9 @@ static hipError_t launch_stream_t(const DecodeArgs& a, const StreamArgs& sp, int
 hipError_t OUSTER_SPEC_FN(launch_decode_stream)(const DecodeArgs& a, const StreamArgs& sp, int tw, int xyzm, int device,
                                                 hipStream_t st) {
     if (sp.lds_bytes > 160 * 1024 || sp.npix_instr > 72) return hipErrorInvalidValue;
+    if (sp.nslot < 2 || sp.nslot > (sp.loader ? STREAM_MAX_SLOTS : 2u) || sp.fixed_off != sp.nslot * sp.ctx_bytes) return hipErrorInvalidValue;
+    for (uint32_t l = 0; l < sp.loader; ++l)   // what a loader's waits count must fit in vmcnt (the plan lowers the depth instead)
+        if ((sp.nslot - 2u) * sp.dma_per_tile[l] > STREAM_MAX_VMCNT) return hipErrorInvalidValue;
     const dim3 grid(8u * a.tiles_per_frame * sp.groups);
     switch (tw) {
         case 128: return launch_stream_t<SpecT, 128>(a, sp, xyzm, grid, device, st);

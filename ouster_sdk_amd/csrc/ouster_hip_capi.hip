@@ -63,9 +63,9 @@ extern "C" {
 
 const char* ouster_hip_last_error(void) { return g_err.c_str(); }
 #ifdef OUSTER_EXPERIMENTS
-const char* ouster_hip_version(void) { return "ouster_hip 0.3 (gfx950) +experiments"; }
+const char* ouster_hip_version(void) { return "ouster_hip 0.4 (gfx950) +experiments"; }
 #else
-const char* ouster_hip_version(void) { return "ouster_hip 0.3 (gfx950)"; }
+const char* ouster_hip_version(void) { return "ouster_hip 0.4 (gfx950)"; }
 #endif
 
 int ouster_hip_ctx_create(int device, void* stream, ouster_hip_ctx** out) {
@@ -671,6 +671,7 @@ int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const u
     }
     in.xyz_mask = (da.xyz[0] ? 1u : 0u) | (da.xyz[1] ? 2u : 0u);
     in.gate_counts = out->gate_counts != nullptr;
+    in.host_ts = da.host_timestamps && da.packet_timestamp;
     in.cus = ctx->cus;
     in.resident_wgs = ctx->resident_wgs;
 #ifdef OUSTER_EXPERIMENTS

@@ -5,7 +5,11 @@ OUSTER_HIP_SO=tools/ab/libouster_hip_<name>.so).
   phase_timing.py small [frames=1]  ONE small launch (1 or 4 frames) on the chip-wide 100 MHz clock (build with -DOUSTER_PHASE_WALL
                                     as well): when workgroups start, where each phase ends, when the fix-up kernel runs
   phase_timing.py fixup             the fix-up pass behind bench.py's stray10 batch (26 of 256 frames flagged) on the same clock
-                                    (OUSTER_HIP_PHASE_FIXUP_ONLY=1 is set here): LEAD / REDO tickets, when they start, how long they take"""
+                                    (OUSTER_HIP_PHASE_FIXUP_ONLY=1 is set here): LEAD / REDO tickets, when they start, how long they take
+  phase_timing.py ring <workload> <frames> stream=<128|256> [knob=value ...]
+                                    the persistent k_decode_stream2: the decoders' wait at the top-of-tile barrier and the loaders'
+                                    request-to-landed time per tile (with a ring deeper than two the loader looks at a tile only when
+                                    it is next in line, so that figure is an upper bound there)"""
 import json, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -106,6 +110,59 @@ def fixup_pass():
     print(json.dumps({"step_ms": round(step_ms, 4), "tile": hp.ctx.last_decode_tile(), "kernel": hp.ctx.last_decode_kernel(), "median_run_us": runs[len(runs) // 2]}))
 
 
+def ring_wait(wl, frames, knobs):
+    """k_decode_stream2, forced by knobs (stream=<tile width>, stream_rows, stream_slots ...): per workgroup, the decoding
+    waves' wait at the top-of-tile barrier as a share of the tile period, and the time from a loader's request of a tile to
+    the moment it saw it landed.  One large launch into a clean stamp buffer, after the step time of 20 launches."""
+    NWG = 1 << 12
+    buf = torch.zeros((NWG, 16), dtype=torch.int64, device="cuda")
+    os.environ["OUSTER_HIP_PHASE_BUF"] = hex(buf.data_ptr())
+    import bench
+    hp, packets, out = bench._workload_setup(wl, frames, pool_frames=16)[:3]
+    hp.ctx.set_knob("tune", 0)
+    for k, v in knobs:
+        hp.ctx.set_knob(k, int(v))
+    for _ in range(10):
+        hp.decode(packets, out)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20):
+        hp.decode(packets, out)
+    e1.record()
+    torch.cuda.synchronize()
+    step_us = e0.elapsed_time(e1) / 20 * 1e3
+    buf.zero_()
+    torch.cuda.synchronize()
+    hp.decode(packets, out)
+    torch.cuda.synchronize()
+    t = buf.cpu().numpy().astype(np.float64)
+    t = t[t[:, 4] != 0]
+    assert hp.ctx.last_decode_kernel() == "k_decode_stream2" and len(t), (hp.ctx.last_decode_kernel(), len(t))
+    life, n = t[:, 1] - t[:, 0], t[:, 4]
+    # one workgroup per CU lives for the whole kernel: the longest life is the kernel, which is the step less a few us
+    mhz = float(np.percentile(life, 99)) / step_us
+    period = life / n
+    pct = lambda v: [round(float(x), 3) for x in np.percentile(v, [5, 25, 50, 75, 95, 100])]
+    many = n > 1
+    res = {"workload": wl, "frames": frames, "knobs": dict(knobs), "kernel": hp.ctx.last_decode_kernel(), "tile": list(hp.ctx.last_decode_tile()),
+           "ring_slots": int(t[0, 6]), "step_us": round(step_us, 2), "workgroups": int(len(t)), "tiles_per_workgroup": pct(n),
+           "ticks_per_us": round(mhz, 2), "percentiles": [5, 25, 50, 75, 95, 100],
+           "tile_period_us": pct(period / mhz),
+           "decoder_wait_per_tile_us": pct(t[many, 2] / (n[many] - 1) / mhz),
+           "decoder_wait_share_of_tile_period": pct(t[many, 2] / (n[many] - 1) / period[many]),
+           "decoder_wait_worst_tile_us": pct(t[many, 5] / mhz),
+           "decoder_wait_first_tile_us": pct(t[:, 3] / mhz),
+           "fetch_request_to_landed_mean_us": pct(t[:, 8] / t[:, 12] / mhz),
+           "fetch_request_to_landed_min_us": pct(t[:, 10] / mhz),
+           "fetch_request_to_landed_max_us": pct(t[:, 9] / mhz),
+           "loader_wait_share_of_life": pct(t[:, 11] / life)}
+    print(json.dumps(res))
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "ring":
+    ring_wait(sys.argv[2], int(sys.argv[3]), [kv.split("=") for kv in sys.argv[4:]])
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "fixup":
     fixup_pass()
     sys.exit(0)
