@@ -94,6 +94,7 @@ oracle:
 cpptests: $(LIB)/libouster_core_amd.so
 	$(MAKE) -C tests/cpp -s
 	$(MAKE) -C tests/cpp -s tonemap_ref_sanitized   # runs it: the host half under ASan / UBSan
+	$(MAKE) -C tests/cpp -f icp_target.mk -s        # the programs of the IcpTarget tests, a makefile of their own
 	$(MAKE) -C oracle -s refcpptests
 
 clean:

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "ouster/algorithm/align_clouds.h"
 #include "ouster/core/image_processing.h"
 #include "ouster/core/lidar_frame.h"
 #include "ouster/core/voxel_hash_map.h"
@@ -292,6 +293,20 @@ class DeviceFrameBatch {
      *         outside the int32 cell grid" (point_to_plane_align: on that route) */
     AlignResult align_voxels(const double* target_points_device, const double* target_normals_device, uint64_t n_target,
                              const double* initial_guess16, const AlignOptions& options = AlignOptions());
+    /** The rows of the last voxel_downsample*() as a resident algorithm::IcpTarget (a project extension, algorithm/align_clouds.h):
+     *  the keyframe or map later batches align against.  With normals when that call produced them.  The target copies what it
+     *  needs and shares ownership of the batch's context, so it may outlive the batch.  options.max_corr_dist is the target's;
+     *  synchronous, on the batch's context.
+     *  @throw std::runtime_error before the first voxel_downsample*(); std::invalid_argument as IcpTarget's constructors */
+    algorithm::IcpTarget make_icp_target(const AlignOptions& options = AlignOptions());
+    /** align_voxels against a resident target: no grid work.  Point to plane when the target has normals (the batch's voxel normals
+     *  are then required), point to point otherwise; max_corr_dist is the target's.  The result equals the overload above on the
+     *  target's arrays bit for bit.  The target may come from another batch or from host arrays: the call runs on the target's
+     *  context, on the GPU both must share.
+     *  @throw std::runtime_error before the first voxel_downsample*()
+     *  @throw std::invalid_argument "DeviceFrameBatch::align_voxels: the target lives on another device"
+     *  @throw std::invalid_argument "icp_target: source 0 has no normals and the target has them" and the messages above */
+    AlignResult align_voxels(const algorithm::IcpTarget& target, const double* initial_guess16, const AlignOptions& options = AlignOptions());
 
     /** Per-column body_to_world poses of one frame (w x 16 doubles, row-major 4x4 each; identity
      *  until set), the input of dewarp(). */

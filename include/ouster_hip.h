@@ -868,6 +868,83 @@ int ouster_hip_icp_timing(ouster_hip_ctx* ctx, int on);
 /* ms[OUSTER_HIP_ICP_PHASES] of the last timed call that reached the GPU; INVALID_ARGUMENT when there was none. */
 int ouster_hip_icp_phase_ms(ouster_hip_ctx* ctx, float* ms);
 
+/* ---- IcpTarget: a resident ICP target and many sources per call ------------------------------- */
+/* A project extension: the reference has no such object.  Scan-to-map and frame-to-keyframe align many sources against one target
+ * that does not change.  ouster_hip_icp_target_create builds the target's hash grid once (the grid of ouster_hip_icp_align) and
+ * keeps what a query reads -- the slots, the gathered rows, their original indices -- in device memory the handle owns;
+ * ouster_hip_icp_target_align then aligns K sources against it in lock step: one launch sequence and one read-back per pass for
+ * all K, whatever K is.  Every source is cut into the runs of ouster_hip_icp_chunk_rows() rows the single call uses, a workgroup
+ * per run, and a source's partial sums are folded in index order: for each source, pose, iterations, solved and correspondences
+ * equal bit for bit those of ouster_hip_icp_align called with that source alone, the target's arrays, and the same max_corr_dist,
+ * angle and guess; for any K and any order of the sources.  No floating-point atomic.
+ * A target's method is fixed by how it was made: with normals it serves point to plane only, without them point to point only
+ * (with normals, other target rows take part).  A target of fewer than 20 rows is legal, needs no context and launches nothing:
+ * every alignment against it returns each source's guess (solved = 0, iterations = 0).
+ * ouster_hip_icp_target_create refuses, before any GPU work and in this order: NULL arguments; "max_corr_dist must be finite and
+ * greater than zero"; "target_points and target_normals must have the same number of rows"; "dtype must be F32 or F64"; "flags
+ * must be 0"; "a row stride is smaller than 3"; "NULL pointer"; more than 2^30 rows (UNSUPPORTED, "icp: more than 2^30 rows").
+ * It synchronises once, so the grid's refusal ("point_to_point_align: target point outside the int32 cell grid", or
+ * "point_to_plane_align: ..." with normals) surfaces there, as INVALID_ARGUMENT.  *out is NULL after every failure.
+ * ouster_hip_icp_target_align / _step refuse before any launch, with every output of every source untouched: NULL arguments;
+ * "icp_target: made by another context"; on a target with normals "max_normal_angle_deg must be finite and in [0, 180]", then
+ * per source "source_points and source_normals must have the same number of rows"; "icp_target: source %u has normals and the
+ * target has none" / "icp_target: source %u has no normals and the target has them"; "dtype must be F32 or F64"; a stride below
+ * 3; NULL points; more than 65 535 sources or more than 2^30 rows in total (UNSUPPORTED).  n_sources == 0 is OK and does nothing.
+ * A source of fewer than 20 rows gets its guess back; the others proceed. */
+typedef struct ouster_hip_icp_target ouster_hip_icp_target;
+typedef struct ouster_hip_icp_target_desc {
+    const void* points;            /* [n][stride] of dtype */
+    const void* normals;           /* [n_normals][normal_stride] of dtype, or NULL: a point-to-point target */
+    uint64_t n, n_normals;         /* n_normals must equal n where normals are given */
+    uint64_t stride, normal_stride;   /* elements per row; 0: 3 */
+    int32_t dtype;                 /* OUSTER_HIP_F32 / OUSTER_HIP_F64 */
+    uint32_t flags;                /* must be 0 */
+    double max_corr_dist;
+} ouster_hip_icp_target_desc;
+typedef struct ouster_hip_icp_target_info {
+    uint64_t rows;                 /* rows given */
+    uint64_t rows_used;            /* rows that take part (finite; with normals a finite normal longer than 1e-12) */
+    uint64_t cells;                /* occupied cells of the grid */
+    uint64_t device_bytes;         /* device memory the handle owns */
+    int32_t has_normals;
+    int32_t reserved;
+    double max_corr_dist;
+} ouster_hip_icp_target_info;
+typedef struct ouster_hip_icp_source {
+    const void* points;            /* [n][stride] of the call's dtype */
+    const void* normals;           /* [n_normals][normal_stride], or NULL */
+    uint64_t n, n_normals;
+    uint64_t stride, normal_stride;   /* elements per row; 0: 3 */
+    double initial_guess[16];      /* row-major 4x4 */
+    /* results (ouster_hip_icp_target_align), as in ouster_hip_icp_desc */
+    double pose[16];
+    uint32_t iterations;
+    uint32_t solved;
+    uint64_t correspondences;
+} ouster_hip_icp_source;
+/* Arrays in device memory.  ctx may be NULL for a target of fewer than 20 rows. */
+int ouster_hip_icp_target_create(ouster_hip_ctx* ctx, const ouster_hip_icp_target_desc* desc, ouster_hip_icp_target** out);
+/* The same with the arrays in host memory (staged like every _host call). */
+int ouster_hip_icp_target_create_host(ouster_hip_ctx* ctx, const ouster_hip_icp_target_desc* desc, ouster_hip_icp_target** out);
+/* NULL: nothing. */
+void ouster_hip_icp_target_destroy(ouster_hip_icp_target* target);
+int ouster_hip_icp_target_info_read(const ouster_hip_icp_target* target, ouster_hip_icp_target_info* info);
+/* sources[n_sources], every array in device memory, all of `dtype` (which may differ from the target's).  Synchronous. */
+int ouster_hip_icp_target_align(ouster_hip_ctx* ctx, const ouster_hip_icp_target* target, ouster_hip_icp_source* sources,
+                                uint32_t n_sources, int32_t dtype, double max_normal_angle_deg);
+/* The same with every array in host memory. */
+int ouster_hip_icp_target_align_host(ouster_hip_ctx* ctx, const ouster_hip_icp_target* target, ouster_hip_icp_source* sources,
+                                     uint32_t n_sources, int32_t dtype, double max_normal_angle_deg);
+/* One pass for every source, source k from poses[k] (16 doubles each, row-major), into outs[k] like ouster_hip_icp_step (nn and r:
+ * device arrays of that source's rows, or NULL).  The sources' results are not written.  A source or a target of fewer than 20
+ * rows: INVALID_ARGUMENT "icp_step: fewer than 20 rows". */
+int ouster_hip_icp_target_step(ouster_hip_ctx* ctx, const ouster_hip_icp_target* target, const ouster_hip_icp_source* sources,
+                               uint32_t n_sources, int32_t dtype, double max_normal_angle_deg, const double* poses,
+                               ouster_hip_icp_step_out* outs);
+/* The chunk table of the many-source route for sources of rows[k] rows (0: no chunk), as {source, first row within the source,
+ * rows} triples in chunks[cap][3]; returns the number of chunks (more than cap: only cap were written).  Plain host code. */
+uint64_t ouster_hip_icp_chunk_table(const uint64_t* rows, uint32_t n_sources, uint32_t* chunks, uint64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

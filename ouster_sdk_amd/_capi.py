@@ -139,6 +139,23 @@ class IcpStepOut(C.Structure):   # ouster_hip_icp_step_out
                 ("next_pose", C.c_double * 16), ("stop", C.c_int32), ("solved", C.c_int32)]
 
 
+class IcpTargetDesc(C.Structure):   # ouster_hip_icp_target_desc
+    _fields_ = [("points", C.c_void_p), ("normals", C.c_void_p), ("n", C.c_uint64), ("n_normals", C.c_uint64),
+                ("stride", C.c_uint64), ("normal_stride", C.c_uint64), ("dtype", C.c_int32), ("flags", C.c_uint32),
+                ("max_corr_dist", C.c_double)]
+
+
+class IcpTargetInfo(C.Structure):   # ouster_hip_icp_target_info
+    _fields_ = [("rows", C.c_uint64), ("rows_used", C.c_uint64), ("cells", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("has_normals", C.c_int32), ("reserved", C.c_int32), ("max_corr_dist", C.c_double)]
+
+
+class IcpSource(C.Structure):   # ouster_hip_icp_source
+    _fields_ = [("points", C.c_void_p), ("normals", C.c_void_p), ("n", C.c_uint64), ("n_normals", C.c_uint64),
+                ("stride", C.c_uint64), ("normal_stride", C.c_uint64), ("initial_guess", C.c_double * 16),
+                ("pose", C.c_double * 16), ("iterations", C.c_uint32), ("solved", C.c_uint32), ("correspondences", C.c_uint64)]
+
+
 class NormalsConsts(C.Structure):   # ouster_hip_normals_consts
     _fields_ = [("px_res_h", C.c_double), ("px_res_v", C.c_double), ("tan_safe", C.c_double), ("target_sq", C.c_double),
                 ("subtent", C.c_double)]
@@ -196,6 +213,10 @@ ABI_SYMBOLS = [
     # ICP
     "ouster_hip_icp_align", "ouster_hip_icp_align_host", "ouster_hip_icp_align_ref", "ouster_hip_icp_step", "ouster_hip_icp_step_ref",
     "ouster_hip_icp_chunk_rows", "ouster_hip_icp_timing", "ouster_hip_icp_phase_ms",
+    # IcpTarget: a resident ICP target and many sources per call
+    "ouster_hip_icp_target_create", "ouster_hip_icp_target_create_host", "ouster_hip_icp_target_destroy",
+    "ouster_hip_icp_target_info_read", "ouster_hip_icp_target_align", "ouster_hip_icp_target_align_host",
+    "ouster_hip_icp_target_step", "ouster_hip_icp_chunk_table",
 ]
 
 _hip = None
@@ -352,6 +373,18 @@ def load_hip(private_path: Optional[str] = None):
         L.ouster_hip_icp_chunk_rows.restype = C.c_uint32
         L.ouster_hip_icp_timing.argtypes = [vp, C.c_int]
         L.ouster_hip_icp_phase_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    if hasattr(L, "ouster_hip_icp_target_create"):
+        dp, sp = C.POINTER(C.c_double), C.POINTER(IcpSource)
+        L.ouster_hip_icp_target_create.argtypes = [vp, C.POINTER(IcpTargetDesc), C.POINTER(vp)]
+        L.ouster_hip_icp_target_create_host.argtypes = [vp, C.POINTER(IcpTargetDesc), C.POINTER(vp)]
+        L.ouster_hip_icp_target_destroy.argtypes = [vp]
+        L.ouster_hip_icp_target_destroy.restype = None
+        L.ouster_hip_icp_target_info_read.argtypes = [vp, C.POINTER(IcpTargetInfo)]
+        L.ouster_hip_icp_target_align.argtypes = [vp, vp, sp, C.c_uint32, C.c_int32, C.c_double]
+        L.ouster_hip_icp_target_align_host.argtypes = [vp, vp, sp, C.c_uint32, C.c_int32, C.c_double]
+        L.ouster_hip_icp_target_step.argtypes = [vp, vp, sp, C.c_uint32, C.c_int32, C.c_double, dp, C.POINTER(IcpStepOut)]
+        L.ouster_hip_icp_chunk_table.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint64]
+        L.ouster_hip_icp_chunk_table.restype = C.c_uint64
     if private_path is None:
         _hip = L
     return L

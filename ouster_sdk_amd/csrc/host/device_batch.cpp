@@ -798,6 +798,32 @@ AlignResult DeviceFrameBatch::align_voxels(const double* target_points_device, c
     return r;
 }
 
+algorithm::IcpTarget DeviceFrameBatch::make_icp_target(const AlignOptions& o) {
+    ScopedContext on_my_context(ctx_);
+    if (!vox_made_) throw std::runtime_error("DeviceFrameBatch::make_icp_target: voxel_downsample() or voxel_downsample_with_normals() first");
+    return algorithm::IcpTarget::from_device(static_cast<const double*>(d_vox_pts_.data()),
+                                             vox_normals_ ? static_cast<const double*>(d_vox_nrm_.data()) : nullptr, vox_count_, o.max_corr_dist);
+}
+
+AlignResult DeviceFrameBatch::align_voxels(const algorithm::IcpTarget& target, const double* initial_guess16, const AlignOptions& o) {
+    ScopedContext on_my_context(ctx_);
+    if (!vox_made_) throw std::runtime_error("DeviceFrameBatch::align_voxels: voxel_downsample() or voxel_downsample_with_normals() first");
+    // the rows stay where they are: a target on another GPU cannot read them.  On the batch's GPU the call runs on the target's own
+    // context, whichever that is; the batch's voxel rows are complete (voxel_downsample*() is synchronous)
+    if (target.device() >= 0 && target.device() != ctx_->device())
+        throw std::invalid_argument("DeviceFrameBatch::align_voxels: the target lives on another device");
+    AlignResult r;
+    r.point_to_plane = target.has_normals();
+    double pose[16];
+    const algorithm::impl::AlignStats s =
+        target.align_device(static_cast<const double*>(d_vox_pts_.data()),
+                            r.point_to_plane && vox_normals_ ? static_cast<const double*>(d_vox_nrm_.data()) : nullptr, vox_count_,
+                            initial_guess16, o.max_normal_angle_deg, pose);
+    r.pose = core::mat4d::FromRowMajor(pose);
+    r.iterations = s.iterations, r.correspondences = s.correspondences, r.solved = s.solved;
+    return r;
+}
+
 double* DeviceFrameBatch::voxels_device() { return vox_made_ ? static_cast<double*>(d_vox_pts_.data()) : nullptr; }
 
 double* DeviceFrameBatch::voxel_normals_device() {

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cfloat>
+#include <cstdio>
 #include <cstring>
 #include <unordered_map>
 #include <vector>
@@ -35,6 +36,65 @@ const char* icp_validate(const ouster_hip_icp_desc* d) {
 const char* icp_msg_grid(IcpMethod m) {
     return m == ICP_PLANE ? "point_to_plane_align: target point outside the int32 cell grid"
                           : "point_to_point_align: target point outside the int32 cell grid";
+}
+
+const char* icp_target_validate(const ouster_hip_icp_target_desc* d) {
+    if (!std::isfinite(d->max_corr_dist) || d->max_corr_dist <= 0.0) return "max_corr_dist must be finite and greater than zero";
+    if (d->normals && d->n != d->n_normals) return "target_points and target_normals must have the same number of rows";
+    if (d->dtype != OUSTER_HIP_F32 && d->dtype != OUSTER_HIP_F64) return "dtype must be F32 or F64";
+    if (d->flags != 0) return "flags must be 0";
+    for (uint64_t s : {d->stride, d->normal_stride})
+        if (s && s < 3) return "a row stride is smaller than 3";
+    if (d->n && !d->points) return "NULL pointer";
+    return nullptr;
+}
+
+int icp_sources_validate(bool target_has_normals, const ouster_hip_icp_source* sources, uint32_t n_sources, int32_t dtype,
+                         double max_normal_angle_deg, char* msg, size_t cap) {
+    auto refuse = [&](int code, const char* text) {
+        std::snprintf(msg, cap, "%s", text);
+        return code;
+    };
+    if (target_has_normals) {
+        if (!std::isfinite(max_normal_angle_deg) || max_normal_angle_deg < 0.0 || max_normal_angle_deg > 180.0)
+            return refuse(OUSTER_HIP_ERR_INVALID_ARGUMENT, "max_normal_angle_deg must be finite and in [0, 180]");
+        for (uint32_t k = 0; k < n_sources; ++k)
+            if (sources[k].normals && sources[k].n != sources[k].n_normals)
+                return refuse(OUSTER_HIP_ERR_INVALID_ARGUMENT, "source_points and source_normals must have the same number of rows");
+    }
+    for (uint32_t k = 0; k < n_sources; ++k)
+        if ((sources[k].normals != nullptr) != target_has_normals) {
+            std::snprintf(msg, cap, target_has_normals ? "icp_target: source %u has no normals and the target has them"
+                                                       : "icp_target: source %u has normals and the target has none", k);
+            return OUSTER_HIP_ERR_INVALID_ARGUMENT;
+        }
+    if (dtype != OUSTER_HIP_F32 && dtype != OUSTER_HIP_F64) return refuse(OUSTER_HIP_ERR_INVALID_ARGUMENT, "dtype must be F32 or F64");
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < n_sources; ++k) {
+        for (uint64_t s : {sources[k].stride, sources[k].normal_stride})
+            if (s && s < 3) return refuse(OUSTER_HIP_ERR_INVALID_ARGUMENT, "a row stride is smaller than 3");
+        if (sources[k].n && !sources[k].points) return refuse(OUSTER_HIP_ERR_INVALID_ARGUMENT, "NULL pointer");
+    }
+    if (n_sources > ICP_MAX_SOURCES) return refuse(OUSTER_HIP_ERR_UNSUPPORTED, "icp_target: more than 65535 sources");
+    for (uint32_t k = 0; k < n_sources; ++k) {
+        if (sources[k].n > ICP_MAX_ROWS) return refuse(OUSTER_HIP_ERR_UNSUPPORTED, "icp: more than 2^30 rows");
+        total += sources[k].n;
+    }
+    if (total > ICP_MAX_ROWS) return refuse(OUSTER_HIP_ERR_UNSUPPORTED, "icp: more than 2^30 rows");
+    return OUSTER_HIP_OK;
+}
+
+uint64_t icp_chunk_table(const uint64_t* rows, uint32_t n_sources, IcpChunk* chunks, uint64_t cap, uint64_t* first_row,
+                         uint64_t* first_chunk) {
+    uint64_t row = 0, at = 0;
+    for (uint32_t k = 0; k < n_sources; ++k) {
+        if (first_row) first_row[k] = row;
+        if (first_chunk) first_chunk[k] = at;
+        for (uint64_t first = 0; first < rows[k]; first += ICP_CHUNK_ROWS, ++at)
+            if (at < cap) chunks[at] = IcpChunk{k, (uint32_t)first, (uint32_t)std::min<uint64_t>(ICP_CHUNK_ROWS, rows[k] - first)};
+        row += rows[k];
+    }
+    return at;
 }
 
 double icp_cos_gate(double max_normal_angle_deg) { return std::cos(max_normal_angle_deg * M_PI / 180.0); }
@@ -416,4 +476,11 @@ extern "C" int ouster_hip_icp_align_ref(ouster_hip_icp_desc* d) {
     std::memcpy(d->pose, solved ? pose : d->initial_guess, sizeof pose);
     d->iterations = iterations, d->solved = solved, d->correspondences = count;
     return OUSTER_HIP_OK;
+}
+
+extern "C" uint64_t ouster_hip_icp_chunk_table(const uint64_t* rows, uint32_t n_sources, uint32_t* chunks, uint64_t cap) {
+    using namespace ouster_hip_dev;
+    static_assert(sizeof(IcpChunk) == 3 * sizeof(uint32_t), "chunks[cap][3]");
+    if (!rows || (cap && !chunks)) return 0;
+    return icp_chunk_table(rows, n_sources, reinterpret_cast<IcpChunk*>(chunks), cap, nullptr, nullptr);
 }

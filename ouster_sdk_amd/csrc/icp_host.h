@@ -39,6 +39,28 @@ bool icp_ldlt6(const double (&h)[6][6], const double (&b)[6], double (&x)[6]);
 void icp_finish_pass(IcpMethod m, uint64_t count, const double* sums, const double* cx, const double* cq, const double* pose16,
                      double* next16, bool* stop);
 
+// ---- IcpTarget: a resident target and many sources per call (ouster_hip_icp_target_*) ----
+constexpr uint32_t ICP_CHUNK_ROWS = 1024;       // k_icp.h: ICP_CHUNK, the rows a workgroup of the sum kernels owns
+constexpr uint32_t ICP_MAX_SOURCES = 65535;
+
+// a run of at most ICP_CHUNK_ROWS rows of one source, starting at a multiple of ICP_CHUNK_ROWS of that source's own rows: what
+// one workgroup of the many-source kernels owns.  The runs of a source are those of the single call, which is why its sums are.
+struct IcpChunk {
+    uint32_t source, first, rows;
+};
+
+// nullptr, or what ouster_hip_icp_target_create refuses `d` with (the checks after the NULL arguments, in the header's order)
+const char* icp_target_validate(const ouster_hip_icp_target_desc* d);
+// OUSTER_HIP_OK, or the code ouster_hip_icp_target_align / _step refuse the sources with and the message in msg[cap]: on a plane
+// target the angle, then the rows of every source's normals; normals on one side only; dtype, strides, NULL points; the two limits
+int icp_sources_validate(bool target_has_normals, const ouster_hip_icp_source* sources, uint32_t n_sources, int32_t dtype,
+                         double max_normal_angle_deg, char* msg, size_t cap);
+// The chunk table of sources of rows[k] rows (0: the source takes no part and gets no chunk): chunks[] in source order, and per
+// source its first row in the concatenated per-row outputs and its first chunk.  Returns the number of chunks; writes at most
+// `cap` of them (chunks may be nullptr with cap 0 to count); first_row / first_chunk may be nullptr.
+uint64_t icp_chunk_table(const uint64_t* rows, uint32_t n_sources, IcpChunk* chunks, uint64_t cap, uint64_t* first_row,
+                         uint64_t* first_chunk);
+
 // the C ABI's error channel (ouster_hip_capi.hip): stores the thread's message, returns `code`
 int fail_msg(int code, const char* msg);
 

@@ -67,10 +67,56 @@ struct IcpArgs {
 
 inline uint32_t icp_chunks(uint32_t n_src) { return (n_src + ICP_CHUNK - 1) / ICP_CHUNK; }
 
+// What a query of the grid reads and writes, whoever owns the grid: the call's workspace (IcpArgs) or a resident target
+// (ouster_hip_icp_target).  The per-row outputs are indexed by the row's place in the (concatenated) outputs.
+struct IcpQuery {
+    int32_t plane;
+    uint32_t table_mask, n_tgt;
+    double inv, max_d2, cos_gate;
+    const IcpSlot* slots;
+    const uint32_t *slot_end, *sidx;
+    const double* rows;
+    int32_t* nn;
+    double* r;
+    uint64_t* key;
+    uint32_t* flag;
+    double* xq;
+};
+
+// ---- many sources against one resident target (ouster_hip_icp_target_align / _step) ----
+static_assert(ICP_CHUNK == ICP_CHUNK_ROWS, "the chunk table of icp_host.h cuts the sources into the sum kernels' runs");
+
+// a row of the source table: written by the host, sent again (poses and flags) once per pass
+struct IcpSource {
+    const void *src, *src_n;   // [n][stride] of f32 / f64
+    uint64_t src_stride, src_n_stride;
+    uint32_t n;                // rows
+    uint32_t first;            // its first row in the concatenated per-row outputs
+    uint32_t first_chunk, chunks;
+    int32_t active, reserved;  // 0: every kernel skips the source and leaves its header alone
+    double pose[16];           // of the pass
+};
+
+struct IcpManyArgs {
+    IcpQuery q;                // the target, the constants, the concatenated per-row outputs [n_rows]
+    const IcpSource* sources;  // [n_sources]
+    const IcpChunk* chunks;    // [n_chunks]
+    const uint32_t *seg_begin, *seg_end;   // [n_sources] a source's rows in the outputs; empty (end == begin) while inactive
+    IcpHeader* hdr;            // [n_sources] what a pass reads back
+    uint32_t* counts;          // [n_sources] the segmented sum of the flags
+    uint64_t* key_sorted;      // [n_rows]
+    double* partials;          // [n_chunks][OUSTER_HIP_ICP_SUMS]
+    uint32_t n_sources, n_chunks, n_rows;
+    int32_t f32;               // of the sources
+    double max_corr_dist;
+};
+
 hipError_t launch_icp_keys(const IcpArgs& a, hipStream_t st);         // keys, pass.status
 hipError_t launch_icp_slots(const IcpArgs& a, hipStream_t st);        // slots, slot_end (after the segments)
 hipError_t launch_icp_gather(const IcpArgs& a, hipStream_t st);       // rows
 hipError_t launch_icp_correspond(const IcpArgs& a, hipStream_t st);   // nn, r, key, flag, xq
+hipError_t launch_icp_rows_used(const IcpArgs& a, hipStream_t st);    // pass.count: the rows that take part (after the grid)
+hipError_t launch_icp_correspond_many(const IcpManyArgs& m, hipStream_t st);   // the same of every active source, a workgroup per chunk
 
 // The device-wide pieces (hipcc only): the bytes of temporary storage a call needs, the grid once per call and one pass, both on the
 // stream without a synchronisation.  `va` carries the target-side arrays for the launchers of k_voxel.h (n = n_tgt).
@@ -79,6 +125,10 @@ hipError_t launch_icp_correspond(const IcpArgs& a, hipStream_t st);   // nn, r, 
 hipError_t icp_temp_bytes(uint32_t n_src, uint32_t n_tgt, size_t* bytes);
 hipError_t icp_grid_run(const IcpArgs& a, const VoxelArgs& va, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t icp_pass_run(const IcpArgs& a, void* temp, size_t temp_bytes, hipStream_t st, hipEvent_t* ev = nullptr);
+// The many-source pass: correspond, a segmented sum of the flags and a segmented radix sort of the keys over the sources' rows,
+// the medians, the sum kernels and a fold per source; the active sources' headers are complete when the stream gets there.
+hipError_t icp_many_temp_bytes(uint32_t n_rows, uint32_t n_sources, size_t* bytes);
+hipError_t icp_many_pass_run(const IcpManyArgs& m, void* temp, size_t temp_bytes, hipStream_t st);
 #endif
 
 }  // namespace ouster_hip_dev

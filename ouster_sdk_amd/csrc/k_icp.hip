@@ -19,6 +19,16 @@
 //                   combines by xor butterfly (6 levels), lane 0 of each wave stores to LDS and one thread per sum folds the waves
 //                   in order: one partial per sum and chunk.  k_icp_fold (one workgroup) folds the partials in index order.  A tree
 //                   of fixed shape, 3 + 6 + 3 additions deep below the partial fold: the result depends on the inputs only.
+// Many sources against a resident target (ouster_hip_icp_target_*): the grid is built once, as above, and what a query reads is
+// kept by the handle.  A pass is one launch sequence for all sources:
+// k_icp_correspond_many, k_icp_sums_point_a_many / _b_many, k_icp_sums_plane_many
+//                   a workgroup per chunk of the chunk table {source, first row within the source, rows}: every source is cut
+//                   into the runs of ICP_CHUNK rows the single call uses, and the bodies are the single call's (correspond_row,
+//                   sums_point, sums_plane, block_sums) with the source's pose, pointers and header.
+// (rocPRIM)         a segmented sum of the flags and a segmented radix sort of the keys, a segment per source.
+// k_icp_median_many a thread per source; k_icp_fold_many: a workgroup per source folds that source's chunks in index order.
+//                   Equal chunking and equal fold order: a source's sums are those of a call of its own, bit for bit.  A chunk of
+//                   an inactive source (fewer than 20 rows, or out of the loop already) returns at once.
 #include <hip/hip_runtime.h>
 
 #include "k_icp.h"
@@ -28,6 +38,8 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_reduce.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/device/device_segmented_reduce.hpp>
 #endif
 
 namespace ouster_hip_dev {
@@ -105,17 +117,24 @@ __global__ void __launch_bounds__(ICP_WG) k_icp_gather(IcpArgs a) {
     }
 }
 
+// the single call's own grid and per-row outputs, as a query reads and writes them
+__device__ __forceinline__ IcpQuery icp_query(const IcpArgs& a) {
+    return IcpQuery{a.plane, a.table_mask, a.n_tgt, a.inv, a.max_d2, a.cos_gate, a.slots, a.slot_end, a.sidx, a.rows,
+                    a.nn, a.r, a.key, a.flag, a.xq};
+}
+
+// One source row against the grid.  `a` carries the target and the call's constants; the source's own pointers, its pose P and
+// its first row `out` in the per-row outputs are the caller's: k_icp_correspond passes those of `a`, k_icp_correspond_many those of
+// the chunk's source.
 template <class T>
-__global__ void __launch_bounds__(ICP_WG) k_icp_correspond(IcpArgs a) {
-    const uint32_t i = blockIdx.x * ICP_WG + threadIdx.x;
-    if (i >= a.n_src) return;
-    const double* P = a.pose;
+__device__ __forceinline__ void correspond_row(const IcpQuery& a, const void* src, uint64_t src_stride, const void* src_n,
+                                               uint64_t src_n_stride, const double* P, uint32_t row, uint64_t out) {
     const uint32_t W = a.plane ? 6u : 3u;
     double p0, p1, p2, m0 = 0.0, m1 = 0.0, m2 = 0.0;
-    load3<T>(a.src, a.src_stride, i, p0, p1, p2);
+    load3<T>(src, src_stride, row, p0, p1, p2);
     bool live = true;
     if (a.plane) {
-        load3<T>(a.src_n, a.src_n_stride, i, m0, m1, m2);
+        load3<T>(src_n, src_n_stride, row, m0, m1, m2);
         const double len = norm3(m0, m1, m2);
         live = finite3(m0, m1, m2) && !(len <= ICP_NORMAL_EPS);
         m0 = m0 / len, m1 = m1 / len, m2 = m2 / len;
@@ -179,32 +198,82 @@ __global__ void __launch_bounds__(ICP_WG) k_icp_correspond(IcpArgs a) {
         if (keep && j < a.n_tgt) nn = (int32_t)j;
     }
     if (nn < 0) r = 0.0, s0 = s1 = s2 = 0.0;
-    a.nn[i] = nn;
-    a.r[i] = r;
-    a.key[i] = nn >= 0 ? (uint64_t)__double_as_longlong(fabs(r)) : ICP_NO_KEY;
-    a.flag[i] = nn >= 0;
-    double* o = a.xq + 6 * (uint64_t)i;
+    a.nn[out] = nn;
+    a.r[out] = r;
+    a.key[out] = nn >= 0 ? (uint64_t)__double_as_longlong(fabs(r)) : ICP_NO_KEY;
+    a.flag[out] = nn >= 0;
+    double* o = a.xq + 6 * out;
     o[0] = x0, o[1] = x1, o[2] = x2, o[3] = s0, o[4] = s1, o[5] = s2;
+}
+
+template <class T>
+__global__ void __launch_bounds__(ICP_WG) k_icp_correspond(IcpArgs a) {
+    const uint32_t i = blockIdx.x * ICP_WG + threadIdx.x;
+    if (i >= a.n_src) return;
+    correspond_row<T>(icp_query(a), a.src, a.src_stride, a.src_n, a.src_n_stride, a.pose, i, i);
+}
+
+// The same for many sources in one launch: a workgroup per chunk of the chunk table, thread t on rows first + t + 256 k of the
+// chunk's source (the map of the sum kernels), with that source's pointers and pose.  A chunk of an inactive source returns at once.
+template <class T>
+__global__ void __launch_bounds__(ICP_WG) k_icp_correspond_many(IcpManyArgs m) {
+    if (blockIdx.x >= m.n_chunks) return;
+    const IcpChunk c = m.chunks[blockIdx.x];
+    if (c.source >= m.n_sources) return;
+    const IcpSource* s = m.sources + c.source;
+    if (!s->active) return;
+    for (uint32_t k = 0; k < ICP_ROWS_PER_THREAD; ++k) {
+        const uint32_t t = threadIdx.x + ICP_WG * k;
+        if (t >= c.rows || c.first + t >= s->n || (uint64_t)s->first + c.first + t >= m.n_rows) continue;
+        correspond_row<T>(m.q, s->src, s->src_stride, s->src_n, s->src_n_stride, s->pose, c.first + t, s->first + c.first + t);
+    }
+}
+
+// one thread, after the grid: the rows that take part are sorted first, so the end of the last cell counts them -> pass.count
+// (what ouster_hip_icp_target_create reports; a pass overwrites it)
+__global__ void k_icp_rows_used(IcpArgs a) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const uint32_t cells = a.rb->grid.n_vox;
+    uint32_t used = 0;
+    if (cells && cells <= a.n_tgt) used = a.seg_end[cells - 1];
+    a.rb->pass.count = used <= a.n_tgt ? used : a.n_tgt;
 }
 
 // What follows the correspondences uses cross-lane operations and several kernel arguments: device only.  The host-lanes build of
 // tests/cpp/icp_lanes.cpp compiles everything above, one thread per lane; these are tests/test_gpu_icp.py's business.
 #ifdef __HIPCC__
-__global__ void k_icp_median(IcpArgs a) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    IcpHeader* h = &a.rb->pass;
-    const uint32_t count = h->count;
+// the median of the `count` smallest of a source's n sorted keys, sigma and the Huber delta -> h
+__device__ __forceinline__ void median_of(IcpHeader* h, uint32_t count, const uint64_t* key_sorted, uint32_t n, double max_corr_dist) {
     double median = 0.0, delta = 0.0;
-    if (count >= ICP_MIN_POINTS && count <= a.n_src) {
+    if (count >= ICP_MIN_POINTS && count <= n) {
         const uint32_t mid = count / 2;
-        const double hi = __longlong_as_double((long long)a.key_sorted[mid]);
-        median = (count & 1u) ? hi : 0.5 * (__longlong_as_double((long long)a.key_sorted[mid - 1]) + hi);
+        const double hi = __longlong_as_double((long long)key_sorted[mid]);
+        median = (count & 1u) ? hi : 0.5 * (__longlong_as_double((long long)key_sorted[mid - 1]) + hi);
         double sigma = 1.4826 * median;
-        if (!__builtin_isfinite(sigma) || sigma < 1e-4) sigma = fmax(1e-3, 0.25 * a.max_corr_dist);
+        if (!__builtin_isfinite(sigma) || sigma < 1e-4) sigma = fmax(1e-3, 0.25 * max_corr_dist);
         delta = 1.5 * sigma;
     }
     h->median = median;
     h->huber_delta = delta;
+}
+
+__global__ void k_icp_median(IcpArgs a) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    IcpHeader* h = &a.rb->pass;
+    median_of(h, h->count, a.key_sorted, a.n_src, a.max_corr_dist);
+}
+
+// one thread per source: the count of the segmented reduction into the source's header, then the same arithmetic
+__global__ void __launch_bounds__(64) k_icp_median_many(IcpManyArgs m) {
+    const uint32_t k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= m.n_sources) return;
+    const IcpSource* s = m.sources + k;
+    if (!s->active || (uint64_t)s->first + s->n > m.n_rows) return;
+    IcpHeader* h = m.hdr + k;
+    const uint32_t count = m.counts[k];
+    h->status = 0;
+    h->count = count;
+    median_of(h, count, m.key_sorted + s->first, s->n, m.max_corr_dist);
 }
 
 __device__ __forceinline__ double huber_weight(double r, double delta) {
@@ -232,11 +301,39 @@ __device__ __forceinline__ void block_sums(double (&acc)[NS], double* partial) {
     }
 }
 
+// the rows a workgroup of the sum kernels folds: rows base + t + 256 k below n of one source, whose per-row outputs start at
+// nn / r / xq; the source's header and where the partial goes
+struct IcpRows {
+    const int32_t* nn;
+    const double *r, *xq;
+    uint64_t base;
+    uint32_t n;
+    const IcpHeader* h;
+    double* partial;   // [OUSTER_HIP_ICP_SUMS] of this chunk
+};
+
+__device__ __forceinline__ IcpRows rows_of(const IcpArgs& a) {
+    return IcpRows{a.nn, a.r, a.xq, (uint64_t)blockIdx.x * ICP_CHUNK, a.n_src, &a.rb->pass,
+                   a.partials + (uint64_t)blockIdx.x * OUSTER_HIP_ICP_SUMS};
+}
+
+// false: the chunk's source is inactive (the whole workgroup leaves)
+__device__ __forceinline__ bool rows_of(const IcpManyArgs& m, IcpRows& v) {
+    if (blockIdx.x >= m.n_chunks) return false;
+    const IcpChunk c = m.chunks[blockIdx.x];
+    if (c.source >= m.n_sources) return false;
+    const IcpSource* s = m.sources + c.source;
+    if (!s->active || (uint64_t)s->first + s->n > m.n_rows) return false;
+    v = IcpRows{m.q.nn + s->first, m.q.r + s->first, m.q.xq + 6 * (uint64_t)s->first, c.first, s->n, m.hdr + c.source,
+                m.partials + (uint64_t)blockIdx.x * OUSTER_HIP_ICP_SUMS};
+    return true;
+}
+
 // mode 0: w, w x, w q.  mode 1: (w (x - cx)_i) (q - cq)_j with the centroids of the header
 template <int MODE>
-__device__ __forceinline__ void sums_point(const IcpArgs& a) {
+__device__ __forceinline__ void sums_point(const IcpRows& a) {
     constexpr int NS = MODE == 0 ? 7 : 9;
-    const IcpHeader* h = &a.rb->pass;
+    const IcpHeader* h = a.h;
     const double delta = h->huber_delta;
     double cx[3] = {0, 0, 0}, cq[3] = {0, 0, 0};
     if (MODE == 1)
@@ -244,10 +341,10 @@ __device__ __forceinline__ void sums_point(const IcpArgs& a) {
     double acc[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) acc[s] = 0.0;
-    const uint64_t base = (uint64_t)blockIdx.x * ICP_CHUNK;
+    const uint64_t base = a.base;
     for (uint32_t k = 0; k < ICP_ROWS_PER_THREAD; ++k) {
         const uint64_t i = base + threadIdx.x + (uint64_t)ICP_WG * k;
-        if (i >= a.n_src || a.nn[i] < 0) continue;
+        if (i >= a.n || a.nn[i] < 0) continue;
         const double w = huber_weight(a.r[i], delta);
         const double* o = a.xq + 6 * i;
         if (MODE == 0) {
@@ -264,22 +361,19 @@ __device__ __forceinline__ void sums_point(const IcpArgs& a) {
                 for (int c = 0; c < 3; ++c) acc[3 * r + c] = acc[3 * r + c] + wx[r] * dq[c];
         }
     }
-    block_sums<NS>(acc, a.partials + (uint64_t)blockIdx.x * OUSTER_HIP_ICP_SUMS + (MODE == 0 ? 0 : 7));
+    block_sums<NS>(acc, a.partial + (MODE == 0 ? 0 : 7));
 }
 
-__global__ void __launch_bounds__(ICP_WG) k_icp_sums_point_a(IcpArgs a) { sums_point<0>(a); }
-__global__ void __launch_bounds__(ICP_WG) k_icp_sums_point_b(IcpArgs a) { sums_point<1>(a); }
-
-__global__ void __launch_bounds__(ICP_WG) k_icp_sums_plane(IcpArgs a) {
+__device__ __forceinline__ void sums_plane(const IcpRows& a) {
     constexpr int NS = 27;
-    const double delta = a.rb->pass.huber_delta;
+    const double delta = a.h->huber_delta;
     double acc[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) acc[s] = 0.0;
-    const uint64_t base = (uint64_t)blockIdx.x * ICP_CHUNK;
+    const uint64_t base = a.base;
     for (uint32_t k = 0; k < ICP_ROWS_PER_THREAD; ++k) {
         const uint64_t i = base + threadIdx.x + (uint64_t)ICP_WG * k;
-        if (i >= a.n_src || a.nn[i] < 0) continue;
+        if (i >= a.n || a.nn[i] < 0) continue;
         const double r = a.r[i], w = huber_weight(r, delta);
         const double* o = a.xq + 6 * i;
         const double j[6] = {o[1] * o[5] - o[2] * o[4], o[2] * o[3] - o[0] * o[5], o[0] * o[4] - o[1] * o[3], o[3], o[4], o[5]};
@@ -291,16 +385,34 @@ __global__ void __launch_bounds__(ICP_WG) k_icp_sums_plane(IcpArgs a) {
 #pragma unroll
         for (int p = 0; p < 6; ++p) acc[21 + p] = acc[21 + p] + (-w) * (j[p] * r);
     }
-    block_sums<NS>(acc, a.partials + (uint64_t)blockIdx.x * OUSTER_HIP_ICP_SUMS);
+    block_sums<NS>(acc, a.partial);
 }
 
-// one workgroup: sum `ofs + t` of the header is the left fold of the chunks' partials in index order; centroids: then cx = sum w x /
-// sum w, cq likewise (the divisions of the reference's loop)
-__global__ void __launch_bounds__(64) k_icp_fold(IcpArgs a, uint32_t ofs, uint32_t ns, uint32_t chunks, int centroids) {
-    IcpHeader* h = &a.rb->pass;
+__global__ void __launch_bounds__(ICP_WG) k_icp_sums_point_a(IcpArgs a) { sums_point<0>(rows_of(a)); }
+__global__ void __launch_bounds__(ICP_WG) k_icp_sums_point_b(IcpArgs a) { sums_point<1>(rows_of(a)); }
+__global__ void __launch_bounds__(ICP_WG) k_icp_sums_plane(IcpArgs a) { sums_plane(rows_of(a)); }
+
+// The many-source forms: a workgroup per chunk of the chunk table, the same per-thread fold and the same tree, into partials[chunk].
+// (The test is uniform over the workgroup: all of it leaves, or all of it reaches the barrier of block_sums.)
+__global__ void __launch_bounds__(ICP_WG) k_icp_sums_point_a_many(IcpManyArgs m) {
+    IcpRows v;
+    if (rows_of(m, v)) sums_point<0>(v);
+}
+__global__ void __launch_bounds__(ICP_WG) k_icp_sums_point_b_many(IcpManyArgs m) {
+    IcpRows v;
+    if (rows_of(m, v)) sums_point<1>(v);
+}
+__global__ void __launch_bounds__(ICP_WG) k_icp_sums_plane_many(IcpManyArgs m) {
+    IcpRows v;
+    if (rows_of(m, v)) sums_plane(v);
+}
+
+// sum `ofs + t` of the header is the left fold of the chunks' partials in index order; centroids: then cx = sum w x / sum w, cq
+// likewise (the divisions of the reference's loop)
+__device__ __forceinline__ void fold_partials(IcpHeader* h, const double* partials, uint32_t ofs, uint32_t ns, uint32_t chunks, int centroids) {
     if (threadIdx.x < ns) {
         double v = 0.0;
-        for (uint32_t c = 0; c < chunks; ++c) v = v + a.partials[(uint64_t)c * OUSTER_HIP_ICP_SUMS + ofs + threadIdx.x];
+        for (uint32_t c = 0; c < chunks; ++c) v = v + partials[(uint64_t)c * OUSTER_HIP_ICP_SUMS + ofs + threadIdx.x];
         h->sums[ofs + threadIdx.x] = v;
     }
     __syncthreads();
@@ -309,6 +421,19 @@ __global__ void __launch_bounds__(64) k_icp_fold(IcpArgs a, uint32_t ofs, uint32
         h->centroid_x[threadIdx.x] = h->sums[1 + threadIdx.x] / w;
         h->centroid_q[threadIdx.x] = h->sums[4 + threadIdx.x] / w;
     }
+}
+
+// one workgroup
+__global__ void __launch_bounds__(64) k_icp_fold(IcpArgs a, uint32_t ofs, uint32_t ns, uint32_t chunks, int centroids) {
+    fold_partials(&a.rb->pass, a.partials, ofs, ns, chunks, centroids);
+}
+
+// one workgroup per source: that source's chunks, in index order
+__global__ void __launch_bounds__(64) k_icp_fold_many(IcpManyArgs m, uint32_t ofs, uint32_t ns, int centroids) {
+    if (blockIdx.x >= m.n_sources) return;
+    const IcpSource* s = m.sources + blockIdx.x;
+    if (!s->active || (uint64_t)s->first_chunk + s->chunks > m.n_chunks) return;
+    fold_partials(m.hdr + blockIdx.x, m.partials + (uint64_t)s->first_chunk * OUSTER_HIP_ICP_SUMS, ofs, ns, s->chunks, centroids);
 }
 
 #endif
@@ -341,6 +466,19 @@ hipError_t launch_icp_correspond(const IcpArgs& a, hipStream_t st) {
     if (a.table_mask < a.n_tgt) return hipErrorInvalidValue;   // more slots than rows: what ends every probe chain
     if (a.f32) hipLaunchKernelGGL(k_icp_correspond<float>, icp_grid(a.n_src), dim3(ICP_WG), 0, st, a);
     else hipLaunchKernelGGL(k_icp_correspond<double>, icp_grid(a.n_src), dim3(ICP_WG), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_icp_rows_used(const IcpArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_icp_rows_used, dim3(1), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_icp_correspond_many(const IcpManyArgs& m, hipStream_t st) {
+    if (m.n_chunks == 0) return hipSuccess;
+    if (m.q.table_mask < m.q.n_tgt) return hipErrorInvalidValue;   // more slots than rows: what ends every probe chain
+    if (m.f32) hipLaunchKernelGGL(k_icp_correspond_many<float>, dim3(m.n_chunks), dim3(ICP_WG), 0, st, m);
+    else hipLaunchKernelGGL(k_icp_correspond_many<double>, dim3(m.n_chunks), dim3(ICP_WG), 0, st, m);
     return hipGetLastError();
 }
 
@@ -382,6 +520,44 @@ hipError_t icp_grid_run(const IcpArgs& a, const VoxelArgs& va, void* temp, size_
     ICP_TRY(launch_voxel_segments(va, st));
     ICP_TRY(launch_icp_slots(a, st));
     return launch_icp_gather(a, st);
+}
+
+hipError_t icp_many_temp_bytes(uint32_t n_rows, uint32_t n_sources, size_t* bytes) {
+    size_t sort = 0, reduce = 0;
+    uint64_t* k = nullptr;
+    uint32_t* u = nullptr;
+    ICP_TRY(rocprim::segmented_radix_sort_keys(nullptr, sort, k, k, n_rows, n_sources, u, u, 0, 64));
+    ICP_TRY(rocprim::segmented_reduce(nullptr, reduce, u, u, n_sources, u, u, rocprim::plus<uint32_t>(), 0u));
+    *bytes = sort > reduce ? sort : reduce;
+    return hipSuccess;
+}
+
+hipError_t icp_many_pass_run(const IcpManyArgs& m, void* temp, size_t temp_bytes, hipStream_t st) {
+    if (m.n_sources == 0 || m.n_chunks == 0 || m.n_rows == 0) return hipErrorInvalidValue;
+    ICP_TRY(launch_icp_correspond_many(m, st));
+    // an inactive source's segment is empty (seg_end == seg_begin): nothing of it is reduced or sorted
+    size_t bytes = temp_bytes;
+    ICP_TRY(rocprim::segmented_reduce(temp, bytes, m.q.flag, m.counts, m.n_sources, m.seg_begin, m.seg_end, rocprim::plus<uint32_t>(), 0u, st));
+    bytes = temp_bytes;
+    ICP_TRY(rocprim::segmented_radix_sort_keys(temp, bytes, m.q.key, m.key_sorted, m.n_rows, m.n_sources, m.seg_begin, m.seg_end, 0, 64, st));
+    hipLaunchKernelGGL(k_icp_median_many, dim3((m.n_sources + 63) / 64), dim3(64), 0, st, m);
+    ICP_TRY(hipGetLastError());
+    if (m.q.plane) {
+        hipLaunchKernelGGL(k_icp_sums_plane_many, dim3(m.n_chunks), dim3(ICP_WG), 0, st, m);
+        ICP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_icp_fold_many, dim3(m.n_sources), dim3(64), 0, st, m, 0u, 27u, 0);
+        ICP_TRY(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(k_icp_sums_point_a_many, dim3(m.n_chunks), dim3(ICP_WG), 0, st, m);
+        ICP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_icp_fold_many, dim3(m.n_sources), dim3(64), 0, st, m, 0u, 7u, 1);
+        ICP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_icp_sums_point_b_many, dim3(m.n_chunks), dim3(ICP_WG), 0, st, m);
+        ICP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_icp_fold_many, dim3(m.n_sources), dim3(64), 0, st, m, 7u, 9u, 0);
+        ICP_TRY(hipGetLastError());
+    }
+    return hipSuccess;
 }
 
 hipError_t icp_pass_run(const IcpArgs& a, void* temp, size_t temp_bytes, hipStream_t st, hipEvent_t* ev) {

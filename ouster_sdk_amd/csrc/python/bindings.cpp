@@ -961,6 +961,86 @@ PYBIND11_MODULE(core, m) {
                   double max_normal_angle_deg) { return run(src, tgt, &src_n, &tgt_n, guess, max_corr_dist, max_normal_angle_deg); },
             py::arg("source_points"), py::arg("target_points"), py::arg("source_normals"), py::arg("target_normals"),
             py::arg("initial_guess") = py::none(), py::arg("max_corr_dist") = 0.25, py::arg("max_normal_angle_deg") = 20.0);
+
+        // IcpTarget (a project extension: the reference has none): the target kept on the GPU, many sources per call
+        using ouster::sdk::algorithm::IcpTarget;
+        struct PyIcpTarget {
+            std::unique_ptr<IcpTarget> t;
+            const IcpTarget& get() const {
+                if (!t) throw std::invalid_argument("IcpTarget: closed");
+                return *t;
+            }
+        };
+        auto rows_of = [](const darr& a, const std::string& name) {
+            if (a.ndim() != 2 || a.shape(1) != 3) throw std::invalid_argument(name + " must be Nx3");
+            return static_cast<size_t>(a.shape(0));
+        };
+        auto align_many = [rows_of](const PyIcpTarget& self, const std::vector<darr>& sources, const py::object& normals,
+                                    const py::object& guesses, double max_normal_angle_deg) {
+            const size_t n = sources.size();
+            std::vector<darr> nrm;
+            if (!normals.is_none()) nrm = normals.cast<std::vector<darr>>();
+            if (!normals.is_none() && nrm.size() != n) throw std::invalid_argument("normals must have one array per source");
+            std::vector<const double*> p(n), q(n);
+            std::vector<size_t> rows(n), nrows(n);
+            static const double none[3] = {0, 0, 0};
+            for (size_t k = 0; k < n; ++k) {
+                rows[k] = rows_of(sources[k], "sources[" + std::to_string(k) + "]"), p[k] = rows[k] ? sources[k].data() : none;
+                if (!normals.is_none()) nrows[k] = rows_of(nrm[k], "normals[" + std::to_string(k) + "]"), q[k] = nrows[k] ? nrm[k].data() : none;
+            }
+            std::vector<double> g;
+            if (!guesses.is_none()) {
+                const std::vector<darr> ga = guesses.cast<std::vector<darr>>();
+                if (ga.size() != n) throw std::invalid_argument("initial_guesses must have one 4x4 per source");
+                g.resize(16 * n);
+                for (size_t k = 0; k < n; ++k) {
+                    if (ga[k].size() != 16) throw std::invalid_argument("initial_guess must be 4x4");
+                    std::memcpy(&g[16 * k], ga[k].data(), 16 * sizeof(double));
+                }
+            }
+            py::array_t<double> out({static_cast<py::ssize_t>(n), py::ssize_t(4), py::ssize_t(4)});
+            self.get().align_arrays(p.data(), rows.data(), normals.is_none() ? nullptr : q.data(), nrows.data(), n,
+                                    g.empty() ? nullptr : g.data(), max_normal_angle_deg, out.mutable_data(), nullptr);
+            return out;
+        };
+        py::class_<PyIcpTarget>(m, "IcpTarget")
+            .def(py::init([rows_of](const darr& points, const py::object& normals, double max_corr_dist) {
+                     const size_t n = rows_of(points, "target_points");
+                     static const double none[3] = {0, 0, 0};
+                     PyIcpTarget self;
+                     if (normals.is_none()) {
+                         self.t.reset(new IcpTarget(IcpTarget::from_arrays(n ? points.data() : none, n, nullptr, 0, max_corr_dist)));
+                     } else {
+                         const darr nr = normals.cast<darr>();
+                         const size_t nn = rows_of(nr, "target_normals");
+                         self.t.reset(new IcpTarget(IcpTarget::from_arrays(n ? points.data() : none, n, nn ? nr.data() : none, nn, max_corr_dist)));
+                     }
+                     return self;
+                 }),
+                 py::arg("target_points"), py::arg("target_normals") = py::none(), py::arg("max_corr_dist") = 0.25)
+            .def("align_many", align_many, py::arg("sources"), py::arg("normals") = py::none(), py::arg("initial_guesses") = py::none(),
+                 py::arg("max_normal_angle_deg") = 20.0)
+            .def(
+                "align",
+                [align_many](const PyIcpTarget& self, const darr& source, const py::object& normals, const py::object& guess,
+                             double max_normal_angle_deg) {
+                    py::object nl = py::none(), gl = py::none();
+                    if (!normals.is_none()) nl = py::make_tuple(normals);
+                    if (!guess.is_none()) gl = py::make_tuple(guess);
+                    const py::array_t<double> all = align_many(self, std::vector<darr>(1, source), nl, gl, max_normal_angle_deg);
+                    py::array_t<double> out({py::ssize_t(4), py::ssize_t(4)});
+                    std::memcpy(out.mutable_data(), all.data(), 16 * sizeof(double));
+                    return out;
+                },
+                py::arg("source_points"), py::arg("source_normals") = py::none(), py::arg("initial_guess") = py::none(),
+                py::arg("max_normal_angle_deg") = 20.0)
+            .def("close", [](PyIcpTarget& self) { self.t.reset(); })
+            .def("__enter__", [](PyIcpTarget& self) -> PyIcpTarget& { return self; })
+            .def("__exit__", [](PyIcpTarget& self, const py::object&, const py::object&, const py::object&) { self.t.reset(); })
+            .def_property_readonly("size", [](const PyIcpTarget& self) { return self.get().size(); })
+            .def_property_readonly("has_normals", [](const PyIcpTarget& self) { return self.get().has_normals(); })
+            .def_property_readonly("device_bytes", [](const PyIcpTarget& self) { return self.get().device_bytes(); })
+            .def_property_readonly("max_corr_dist", [](const PyIcpTarget& self) { return self.get().max_corr_dist(); });
     }
 
     // extension over the reference's Python surface: the C++ dewarp(LidarFrame, XYZLut, min_range,
