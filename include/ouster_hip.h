@@ -453,8 +453,13 @@ int ouster_hip_ctx_scratch(ouster_hip_ctx* ctx, uint32_t slot, size_t bytes, voi
  *
  * ouster_hip_image_dark_rows: the order statistics of compute_dark_count (:427-460).  Over the columns that hold at least one
  *   pixel != 0 (n_cols of them), for every row i >= 1 the n_cols / 2-th smallest of image(i, c) - image(i - 1, c):
- *   medians [n_images][h - 1] of T (all 0 when n_cols == 0), n_cols [n_images] (nullable).  w <= 4096 (UNSUPPORTED beyond);
- *   a non-empty image with h < 2 has no row pair: INVALID_ARGUMENT (n_images, h or w == 0: OK, nothing is written).
+ *   medians [n_images][h - 1] of T (all 0 when n_cols == 0), n_cols [n_images] (nullable).
+ *   LIMIT: w <= 4096 columns (the kernel keeps one row of keys in LDS).  A wider image is refused with OUSTER_HIP_ERR_UNSUPPORTED
+ *   before anything is launched or written; the reference has no such limit.  BeamUniformityCorrector::update / update_batch
+ *   then throw std::runtime_error, with the image, the dark counts and the call counter as they were (a call that needs no new
+ *   dark counts -- the height is known and it is not the 8th update -- does not reach this function and still succeeds).
+ *   ouster_hip_image_percentiles and ouster_hip_image_apply, and so AutoExposure, take any width.
+ *   A non-empty image with h < 2 has no row pair: INVALID_ARGUMENT (n_images, h or w == 0: OK, nothing is written).
  * ouster_hip_image_percentiles: the order statistics of AutoExposure::apply (:224-252).  The sample is every 4th element of the
  *   flat image, with `dark` (T [n_images][h], nullable) first corrected to max(x - dark[row], 0), kept when > 0:
  *   n [n_images] = its size, lo_hi [n_images][2] of T = its floor(n * lo_percentile)-th and (n - floor(n * hi_percentile) - 1)-th
