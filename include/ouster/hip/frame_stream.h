@@ -27,7 +27,7 @@ struct StreamOptions {
     uint32_t batches_in_flight = 3;   ///< pinned + device buffer sets (>= 2 to overlap)
     BatchOptions outputs;             ///< what the GPU produces (planes / destaggered / xyz)
     bool download_xyz = true;         ///< which of it comes back to the host
-    std::vector<std::string> download_planes;
+    std::vector<std::string> download_planes;   ///< kept staggered planes (outputs.planes); another name: std::invalid_argument
     std::vector<std::string> download_destaggered;
     bool download_headers = true;     ///< timestamp / measurement_id / status per column
     int device = -1;                  ///< GPU to stream through (-1: hip::current_device())
@@ -37,7 +37,8 @@ struct StreamOptions {
     /// in push order, the reference's order inside a frame; 12 B per KEPT point instead of 24 B per pixel for two dense
     /// clouds) is returned in BatchResult::points -- the stream is bound by the link from the device, and this is the route
     /// that moves fewer bytes over it (set download_xyz = false with it).  Poses are the identity: the points are in the frame
-    /// of the LUT (sensor, or body with the extrinsics folded in).
+    /// of the LUT (sensor, or body with the extrinsics folded in).  The route reads the staggered RANGE plane: the constructor
+    /// turns outputs.xyz on for it and, when outputs.planes is a list without RANGE, adds RANGE to the kept planes.
     double dewarp_min_range = 0.0, dewarp_max_range = -1.0;
     bool dewarp_provenance = false;   ///< also frame / column index and timestamp per point
 };

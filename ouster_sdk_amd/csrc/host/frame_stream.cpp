@@ -70,18 +70,27 @@ FrameStream::FrameStream(const std::vector<core::SensorInfo>& sensors, const Str
         opt_.outputs.xyz = true;
         opt_.outputs.gate_min_range = opt_.dewarp_min_range;
         opt_.outputs.gate_max_range = opt_.dewarp_max_range;
+        // ... and so is the staggered RANGE plane, which a list of planes without it would decode but not keep
+        auto& kept = opt_.outputs.planes;
+        if (!kept.empty() && std::find(kept.begin(), kept.end(), std::string(core::ChanField::RANGE)) == kept.end())
+            kept.emplace_back(core::ChanField::RANGE);
     }
     opt_.outputs.context = ctx_;
-    hipStream_t a = nullptr, b = nullptr;
-    ok(hipStreamCreateWithFlags(&a, hipStreamNonBlocking), "hipStreamCreate");
-    ok(hipStreamCreateWithFlags(&b, hipStreamNonBlocking), "hipStreamCreate");
-    stream_h2d_ = a;
-    stream_d2h_ = b;
     for (uint32_t i = 0; i < opt_.batches_in_flight; ++i) {
         auto s = std::make_unique<Slot>();
         s->batch = std::make_unique<DeviceFrameBatch>(sensors, opt_.frames_per_batch, opt_.outputs);
         DeviceFrameBatch& bt = *s->batch;
         const size_t n = opt_.frames_per_batch;
+        // a plane that is decoded (for the cloud, or destaggered only) but not kept staggered cannot be downloaded: say so here,
+        // before a stream, an event or a pinned buffer exists, not at the first submit()
+        for (const auto& name : opt_.download_planes) {
+            try {
+                (void)bt.plane_device(name);
+            } catch (const std::out_of_range&) {
+                throw std::invalid_argument("FrameStream: download_planes names '" + name +
+                                            "', which the batch does not keep as a staggered plane (outputs.planes)");
+            }
+        }
         s->packets.alloc(n * bt.slots_per_frame() * bt.packet_stride());
         std::memset(s->packets.p, 0, s->packets.n);
         if (opt_.download_xyz)
@@ -113,6 +122,11 @@ FrameStream::FrameStream(const std::vector<core::SensorInfo>& sensors, const Str
         ok(hipEventCreateWithFlags(&s->e_pts, hipEventDisableTiming), "hipEventCreate");
         slots_.push_back(std::move(s));
     }
+    hipStream_t a = nullptr, b = nullptr;
+    ok(hipStreamCreateWithFlags(&a, hipStreamNonBlocking), "hipStreamCreate");
+    ok(hipStreamCreateWithFlags(&b, hipStreamNonBlocking), "hipStreamCreate");
+    stream_h2d_ = a;
+    stream_d2h_ = b;
 }
 
 FrameStream::~FrameStream() {
@@ -132,6 +146,8 @@ void FrameStream::push_frame(const std::vector<const uint8_t*>& lidar_packets) {
     Slot& s = *slots_[cur_];
     if (s.in_flight) deliver(s);  // every buffer set busy: the oldest batch has to come home first
     DeviceFrameBatch& bt = *s.batch;
+    if (s.filled >= opt_.frames_per_batch)   // submit() leaves no slot full, even when it throws: never write past the pinned buffer
+        throw std::logic_error("FrameStream::push_frame: the current buffer set is full");
     if (s.filled == 0) s.first_frame = pushed_;
     uint8_t* base = static_cast<uint8_t*>(s.packets.p) +
                     static_cast<size_t>(s.filled) * bt.slots_per_frame() * bt.packet_stride();
@@ -210,9 +226,13 @@ void FrameStream::submit(Slot& s) {
     ScopedContext on_my_context(ctx_);
     DeviceFrameBatch& bt = *s.batch;
     const size_t per_frame = static_cast<size_t>(bt.slots_per_frame()) * bt.packet_stride();
-    if (s.filled < opt_.frames_per_batch)  // partial batch: the unused frames decode to "empty"
-        std::memset(static_cast<uint8_t*>(s.packets.p) + s.filled * per_frame, 0,
-                    (opt_.frames_per_batch - s.filled) * per_frame);
+    // the slot's count goes back to zero before the first call that can throw: a caller who catches what a call below throws and
+    // pushes on starts the slot again instead of writing behind its last frame
+    const uint32_t filled = s.filled;
+    s.filled = 0;
+    if (filled < opt_.frames_per_batch)  // partial batch: the unused frames decode to "empty"
+        std::memset(static_cast<uint8_t*>(s.packets.p) + filled * per_frame, 0,
+                    (opt_.frames_per_batch - filled) * per_frame);
     auto h2d = static_cast<hipStream_t>(stream_h2d_);
     auto d2h = static_cast<hipStream_t>(stream_d2h_);
     auto comp = static_cast<hipStream_t>(ctx_->stream());
@@ -244,8 +264,7 @@ void FrameStream::submit(Slot& s) {
     ok(hipEventRecord(s.e_done, d2h), "hipEventRecord");
     s.in_flight = true;
     s.points_requested = false;
-    s.n_frames = s.filled;
-    s.filled = 0;
+    s.n_frames = filled;
     cur_ = (cur_ + 1) % slots_.size();
 }
 
