@@ -308,6 +308,25 @@ class DeviceFrameBatch {
      *  @throw std::invalid_argument "icp_target: source 0 has no normals and the target has them" and the messages above */
     AlignResult align_voxels(const algorithm::IcpTarget& target, const double* initial_guess16, const AlignOptions& options = AlignOptions());
 
+    /** The scan-to-map steps on resident data (core/voxel_hash_map.h; csrc/k_voxel_map.hip): the rows of the last
+     *  voxel_downsample*() go into a resident core::VoxelHashMap3d without leaving HBM.  add_voxels_to is map.add_points(rows),
+     *  update_voxel_map is map.update(rows, position3); both equal tests/voxel_map_model.py on download_voxels()'s rows.  The calls
+     *  run on the map's context, on the GPU both must share, and are synchronous.
+     *  @throw std::runtime_error before the first voxel_downsample*()
+     *  @throw std::invalid_argument "DeviceFrameBatch: the map lives on another device" (a host map lives on none), and the map's own */
+    void add_voxels_to(core::VoxelHashMap3d& map);
+    void update_voxel_map(core::VoxelHashMap3d& map, const double* position3);
+    /** map.get_closest_neighbors over the same rows: one neighbour and one squared distance per voxel row stay in HBM
+     *  (map_neighbors_device(): double [voxel_count()][3]; map_neighbor_dist_device(): double [voxel_count()]); a row without a
+     *  neighbour below max_distance_sq has (0, 0, 0) and max_distance_sq.  Throws as above. */
+    void closest_in(const core::VoxelHashMap3d& map, double max_distance_sq = DBL_MAX);
+    /** nullptr before the first closest_in() and after a voxel_downsample*() since */
+    double* map_neighbors_device();
+    double* map_neighbor_dist_device();
+    /** Copy them to the host (voxel_count() x 3 and voxel_count() doubles; null pointers are skipped; synchronous).
+     *  @throw std::invalid_argument before closest_in() */
+    void download_map_neighbors(double* points, double* dist_sq);
+
     /** Per-column body_to_world poses of one frame (w x 16 doubles, row-major 4x4 each; identity
      *  until set), the input of dewarp(). */
     void upload_poses(uint32_t frame, const double* poses_w_by_16);
@@ -382,6 +401,9 @@ class DeviceFrameBatch {
     uint64_t vox_count_ = 0;
     bool vox_made_ = false, vox_normals_ = false;
     uint64_t voxel_run_(const void* points, const double* normals, uint64_t n, double voxel_size, const VoxelOptions& o);
+    DeviceBuffer d_map_nn_, d_map_d2_;     // closest_in(): f64 [vox_count_][3] and [vox_count_]
+    bool map_nn_made_ = false;
+    void* voxel_map_handle_(const core::VoxelHashMap3d& map, const char* who);
     bool dw_prov_ = false;
 };
 

@@ -950,6 +950,84 @@ int ouster_hip_icp_target_step(ouster_hip_ctx* ctx, const ouster_hip_icp_target*
  * rows} triples in chunks[cap][3]; returns the number of chunks (more than cap: only cap were written).  Plain host code. */
 uint64_t ouster_hip_icp_chunk_table(const uint64_t* rows, uint32_t n_sources, uint32_t* chunks, uint64_t cap);
 
+/* ---- VoxelHashMap3d: a resident, updatable voxel map ------------------------------------------ */
+/* Replaces ouster::sdk::core::VoxelHashMap3d (ouster_core/include/ouster/core/voxel_hash_map.h:352-516,
+ * ouster_core/src/voxel_hash_map.cpp:13-226; Vector3i / Vector3d / DefaultVoxelBucket / first_n_point).  Every result equals
+ * tests/voxel_map_model.py bit for bit.  The handle owns dense arrays indexed by voxel id -- the id is the creation order: cell,
+ * count, max_points_per_voxel points of 3 doubles -- and an open-addressing table of voxel ids with a power of two of slots, at
+ * least twice the voxel capacity (k_voxel_map.hip).  The arrays grow by doubling once a call's new voxels are counted and before
+ * anything is published; a removal compacts into a second set of arrays of the same capacity and rebuilds the table.  Per-call
+ * intermediates live in the context's voxel workspace.  No floating-point atomic.  Calls on one map are synchronous and not
+ * thread-safe.
+ * Deviations from the reference: rows of _pointcloud and _extract_far come voxel by voxel in creation order (earlier calls first,
+ * first-seen input order within a call), a voxel's points in admission order, survivors of a removal in their old order (the
+ * reference: its hash map's iteration order); a squared distance is ((dx dx + dy dy) + dz dz) (Eigen leaves the order open);
+ * _update checks its position before it adds; and what is undefined there is refused or defined here, below.
+ * ouster_hip_voxel_map_create refuses, before any GPU work and in this order: NULL arguments; "max_points_per_voxel must be greater
+ * than 0"; "voxel_size must be greater than 0" (also a non-finite one); "max_distance must be greater than 0" (also a non-finite
+ * one); "num_attributes must be 0 for a fixed-size PointType"; "voxel map: max_distance / voxel_size exceeds the int32 voxel grid"
+ * (ceil(max_distance / voxel_size) + 1 above 2^31 - 1); unknown flags; a NULL ctx without OUSTER_HIP_VOXEL_MAP_HOST.
+ * _add_points / _update refuse before any GPU work: NULL map; "dtype must be F32 or F64"; "row_stride is smaller than 3"; (update)
+ * a position outside the grid, "voxel map: point outside the int32 voxel grid"; n == 0 does nothing; a NULL array; more than 2^30
+ * rows (UNSUPPORTED).  Refused by the kernels with the map unchanged: a row with a non-finite coordinate or a cell no int32
+ * holds, "voxel map: point outside the int32 voxel grid".  _remove_far / _extract_far refuse an origin outside the grid the same
+ * way.  An output with too little capacity writes nothing, changes nothing, reports the rows needed in *n_out and returns
+ * INVALID_ARGUMENT "voxel map: out_capacity is too small". */
+#define OUSTER_HIP_VOXEL_MAP_HOST 1u   /* flags: the map lives in host memory and runs host/voxel_map_util.cpp on one core; needs no
+                                          context, and every array of every call is host memory (both forms of a call) */
+typedef struct ouster_hip_voxel_map ouster_hip_voxel_map;
+typedef struct ouster_hip_voxel_map_desc {
+    double voxel_size;
+    double max_distance;              /* the reference's default: 100 */
+    uint64_t max_points_per_voxel;    /* the reference's default: 20 */
+    uint64_t min_pts_threshold;       /* accepted, no effect (as in the reference for this bucket type) */
+    uint64_t num_attributes;          /* must be 0 */
+    uint32_t flags;                   /* 0 or OUSTER_HIP_VOXEL_MAP_HOST */
+    uint32_t reserved;
+} ouster_hip_voxel_map_desc;
+typedef struct ouster_hip_voxel_map_info {
+    uint64_t voxels;                  /* voxels held */
+    uint64_t points;                  /* points held */
+    uint64_t voxel_capacity;          /* voxels the arrays hold before they grow */
+    uint64_t points_per_voxel;        /* max_points_per_voxel */
+    uint64_t device_bytes;            /* device memory the handle owns (0 for a host map) */
+} ouster_hip_voxel_map_info;
+/* ctx may be NULL only with OUSTER_HIP_VOXEL_MAP_HOST.  The context must outlive the map.  *out is NULL after a failure. */
+int ouster_hip_voxel_map_create(ouster_hip_ctx* ctx, const ouster_hip_voxel_map_desc* desc, ouster_hip_voxel_map** out);
+/* NULL: nothing. */
+void ouster_hip_voxel_map_destroy(ouster_hip_voxel_map* map);
+/* Forgets every voxel; keeps the capacity. */
+int ouster_hip_voxel_map_clear(ouster_hip_voxel_map* map);
+/* Room for `voxels` voxels: a later call that stays within it allocates nothing.  Never shrinks. */
+int ouster_hip_voxel_map_reserve(ouster_hip_voxel_map* map, uint64_t voxels);
+int ouster_hip_voxel_map_info_read(const ouster_hip_voxel_map* map, ouster_hip_voxel_map_info* info);
+/* add_points: points[n][row_stride] of dtype in device memory (row_stride 0: 3), taken in input order. */
+int ouster_hip_voxel_map_add_points(ouster_hip_voxel_map* map, const void* points, int32_t dtype, uint64_t n, uint64_t row_stride);
+/* The same with the rows in host memory: pool memory in place, anything else through the context's scratch. */
+int ouster_hip_voxel_map_add_points_host(ouster_hip_voxel_map* map, const void* points, int32_t dtype, uint64_t n, uint64_t row_stride);
+/* remove_voxels_far_from_location: origin[3] in host memory. */
+int ouster_hip_voxel_map_remove_far(ouster_hip_voxel_map* map, const double* origin);
+/* extract_voxels_far_from_location: the same, and the erased points to out[out_capacity][3] (device memory); *n_out: their number. */
+int ouster_hip_voxel_map_extract_far(ouster_hip_voxel_map* map, const double* origin, double* out, uint64_t out_capacity, uint64_t* n_out);
+int ouster_hip_voxel_map_extract_far_host(ouster_hip_voxel_map* map, const double* origin, double* out, uint64_t out_capacity, uint64_t* n_out);
+/* update: add_points, then remove_voxels_far_from_location(position). */
+int ouster_hip_voxel_map_update(ouster_hip_voxel_map* map, const void* points, int32_t dtype, uint64_t n, uint64_t row_stride,
+                                const double* position);
+int ouster_hip_voxel_map_update_host(ouster_hip_voxel_map* map, const void* points, int32_t dtype, uint64_t n, uint64_t row_stride,
+                                     const double* position);
+/* pointcloud: every point to out[out_capacity][3]; *n_out: their number. */
+int ouster_hip_voxel_map_pointcloud(const ouster_hip_voxel_map* map, double* out, uint64_t out_capacity, uint64_t* n_out);
+int ouster_hip_voxel_map_pointcloud_host(const ouster_hip_voxel_map* map, double* out, uint64_t out_capacity, uint64_t* n_out);
+/* get_closest_neighbor for queries[q][row_stride] of dtype, one thread each (voxel_hash_map.cpp:158-215 operation for operation: the
+ * 27 cells in VOXEL_SHIFTS order, the lower-bound prune, a voxel's points in admission order, replaced on strict <).
+ * out_points[q][3], out_dist_sq[q]; no neighbour: (0, 0, 0) and max_distance_sq.  A neighbour cell no int32 holds is skipped; a
+ * non-finite query or one outside the grid has no neighbour.  Refused: NULL map; dtype; stride; q > 0 with a NULL array; more than
+ * 2^30 queries (UNSUPPORTED). */
+int ouster_hip_voxel_map_closest(const ouster_hip_voxel_map* map, const void* queries, int32_t dtype, uint64_t q, uint64_t row_stride,
+                                 double max_distance_sq, double* out_points, double* out_dist_sq);
+int ouster_hip_voxel_map_closest_host(const ouster_hip_voxel_map* map, const void* queries, int32_t dtype, uint64_t q,
+                                      uint64_t row_stride, double max_distance_sq, double* out_points, double* out_dist_sq);
+
 #ifdef __cplusplus
 }
 #endif

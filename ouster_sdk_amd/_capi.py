@@ -156,6 +156,18 @@ class IcpSource(C.Structure):   # ouster_hip_icp_source
                 ("pose", C.c_double * 16), ("iterations", C.c_uint32), ("solved", C.c_uint32), ("correspondences", C.c_uint64)]
 
 
+class VoxelMapDesc(C.Structure):   # ouster_hip_voxel_map_desc
+    _fields_ = [("voxel_size", C.c_double), ("max_distance", C.c_double), ("max_points_per_voxel", C.c_uint64),
+                ("min_pts_threshold", C.c_uint64), ("num_attributes", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class VoxelMapInfo(C.Structure):   # ouster_hip_voxel_map_info
+    _fields_ = [(n, C.c_uint64) for n in ("voxels", "points", "voxel_capacity", "points_per_voxel", "device_bytes")]
+
+
+VOXEL_MAP_HOST = 1   # OUSTER_HIP_VOXEL_MAP_HOST
+
+
 class NormalsConsts(C.Structure):   # ouster_hip_normals_consts
     _fields_ = [("px_res_h", C.c_double), ("px_res_v", C.c_double), ("tan_safe", C.c_double), ("target_sq", C.c_double),
                 ("subtent", C.c_double)]
@@ -217,6 +229,12 @@ ABI_SYMBOLS = [
     "ouster_hip_icp_target_create", "ouster_hip_icp_target_create_host", "ouster_hip_icp_target_destroy",
     "ouster_hip_icp_target_info_read", "ouster_hip_icp_target_align", "ouster_hip_icp_target_align_host",
     "ouster_hip_icp_target_step", "ouster_hip_icp_chunk_table",
+    # VoxelHashMap3d: a resident, updatable voxel map
+    "ouster_hip_voxel_map_create", "ouster_hip_voxel_map_destroy", "ouster_hip_voxel_map_clear", "ouster_hip_voxel_map_reserve",
+    "ouster_hip_voxel_map_info_read", "ouster_hip_voxel_map_add_points", "ouster_hip_voxel_map_add_points_host",
+    "ouster_hip_voxel_map_remove_far", "ouster_hip_voxel_map_extract_far", "ouster_hip_voxel_map_extract_far_host",
+    "ouster_hip_voxel_map_update", "ouster_hip_voxel_map_update_host", "ouster_hip_voxel_map_pointcloud",
+    "ouster_hip_voxel_map_pointcloud_host", "ouster_hip_voxel_map_closest", "ouster_hip_voxel_map_closest_host",
 ]
 
 _hip = None
@@ -385,6 +403,25 @@ def load_hip(private_path: Optional[str] = None):
         L.ouster_hip_icp_target_step.argtypes = [vp, vp, sp, C.c_uint32, C.c_int32, C.c_double, dp, C.POINTER(IcpStepOut)]
         L.ouster_hip_icp_chunk_table.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint64]
         L.ouster_hip_icp_chunk_table.restype = C.c_uint64
+    if hasattr(L, "ouster_hip_voxel_map_create"):
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        L.ouster_hip_voxel_map_create.argtypes = [vp, C.POINTER(VoxelMapDesc), C.POINTER(vp)]
+        L.ouster_hip_voxel_map_destroy.argtypes = [vp]
+        L.ouster_hip_voxel_map_destroy.restype = None
+        L.ouster_hip_voxel_map_clear.argtypes = [vp]
+        L.ouster_hip_voxel_map_reserve.argtypes = [vp, C.c_uint64]
+        L.ouster_hip_voxel_map_info_read.argtypes = [vp, C.POINTER(VoxelMapInfo)]
+        for name in ("ouster_hip_voxel_map_add_points", "ouster_hip_voxel_map_add_points_host"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int32, C.c_uint64, C.c_uint64]
+        L.ouster_hip_voxel_map_remove_far.argtypes = [vp, dp]
+        for name in ("ouster_hip_voxel_map_extract_far", "ouster_hip_voxel_map_extract_far_host"):
+            getattr(L, name).argtypes = [vp, dp, vp, C.c_uint64, up]
+        for name in ("ouster_hip_voxel_map_update", "ouster_hip_voxel_map_update_host"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int32, C.c_uint64, C.c_uint64, dp]
+        for name in ("ouster_hip_voxel_map_pointcloud", "ouster_hip_voxel_map_pointcloud_host"):
+            getattr(L, name).argtypes = [vp, vp, C.c_uint64, up]
+        for name in ("ouster_hip_voxel_map_closest", "ouster_hip_voxel_map_closest_host"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_double, vp, vp]
     if private_path is None:
         _hip = L
     return L

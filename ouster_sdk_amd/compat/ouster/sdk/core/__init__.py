@@ -16,6 +16,7 @@ voxel_downsample_3d = _core.voxel_downsample_3d
 voxel_downsample_xd = _core.voxel_downsample_xd
 voxel_downsample = _core.voxel_downsample_xd
 VoxelDownsampleStrategy = _core.VoxelDownsampleStrategy
+VoxelHashMap3d = _core.VoxelHashMap3d   # the resident, updatable voxel map (csrc/k_voxel_map.hip)
 
 
 class ChanField:

@@ -736,7 +736,7 @@ uint64_t DeviceFrameBatch::voxel_run_(const void* points, const double* normals,
     d.strategy = static_cast<int32_t>(o.strategy);
     // a call that throws leaves no result: the earlier one is given up before the buffers may move
     vox_count_ = 0;
-    vox_made_ = vox_normals_ = false;
+    vox_made_ = vox_normals_ = map_nn_made_ = false;
     if (!normals && o.strategy != core::VoxelDownsampleStrategy::AVERAGE_POINT && o.max_points_per_voxel > 1)
         throw std::runtime_error("DeviceFrameBatch::voxel_downsample: FIRST_N_POINT / RANDOM with max_points_per_voxel > 1 are "
                                  "sequential host code (core::voxel_downsample_3d on downloaded points)");
@@ -822,6 +822,57 @@ AlignResult DeviceFrameBatch::align_voxels(const algorithm::IcpTarget& target, c
     r.pose = core::mat4d::FromRowMajor(pose);
     r.iterations = s.iterations, r.correspondences = s.correspondences, r.solved = s.solved;
     return r;
+}
+
+void* DeviceFrameBatch::voxel_map_handle_(const core::VoxelHashMap3d& map, const char* who) {
+    if (!vox_made_) throw std::runtime_error(std::string("DeviceFrameBatch::") + who + ": voxel_downsample() or voxel_downsample_with_normals() first");
+    // the rows stay where they are: a map on another GPU, or in host memory, cannot read them
+    if (map.device() != ctx_->device()) throw std::invalid_argument("DeviceFrameBatch: the map lives on another device");
+    if (!map.handle()) throw std::runtime_error("VoxelHashMap3d: moved from");
+    return map.handle();
+}
+
+namespace {
+void raise_map(int rc) {
+    if (rc == OUSTER_HIP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(ouster_hip_last_error());
+    if (rc != OUSTER_HIP_OK) throw std::runtime_error(ouster_hip_last_error());
+}
+}  // namespace
+
+void DeviceFrameBatch::add_voxels_to(core::VoxelHashMap3d& map) {
+    ScopedContext on_my_context(ctx_);
+    auto* h = static_cast<ouster_hip_voxel_map*>(voxel_map_handle_(map, "add_voxels_to"));
+    raise_map(ouster_hip_voxel_map_add_points(h, d_vox_pts_.data(), OUSTER_HIP_F64, vox_count_, 3));
+}
+
+void DeviceFrameBatch::update_voxel_map(core::VoxelHashMap3d& map, const double* position3) {
+    ScopedContext on_my_context(ctx_);
+    auto* h = static_cast<ouster_hip_voxel_map*>(voxel_map_handle_(map, "update_voxel_map"));
+    raise_map(ouster_hip_voxel_map_update(h, d_vox_pts_.data(), OUSTER_HIP_F64, vox_count_, 3, position3));
+}
+
+void DeviceFrameBatch::closest_in(const core::VoxelHashMap3d& map, double max_distance_sq) {
+    ScopedContext on_my_context(ctx_);
+    auto* h = static_cast<ouster_hip_voxel_map*>(voxel_map_handle_(map, "closest_in"));
+    map_nn_made_ = false;
+    if (vox_count_) {
+        if (d_map_nn_.size() < vox_count_ * 24) d_map_nn_.resize(vox_count_ * 24);
+        if (d_map_d2_.size() < vox_count_ * 8) d_map_d2_.resize(vox_count_ * 8);
+    }
+    raise_map(ouster_hip_voxel_map_closest(h, d_vox_pts_.data(), OUSTER_HIP_F64, vox_count_, 3, max_distance_sq,
+                                           static_cast<double*>(d_map_nn_.data()), static_cast<double*>(d_map_d2_.data())));
+    map_nn_made_ = true;
+}
+
+double* DeviceFrameBatch::map_neighbors_device() { return map_nn_made_ ? static_cast<double*>(d_map_nn_.data()) : nullptr; }
+double* DeviceFrameBatch::map_neighbor_dist_device() { return map_nn_made_ ? static_cast<double*>(d_map_d2_.data()) : nullptr; }
+
+void DeviceFrameBatch::download_map_neighbors(double* points, double* dist_sq) {
+    ScopedContext on_my_context(ctx_);
+    if (!map_nn_made_) throw std::invalid_argument("DeviceFrameBatch::download_map_neighbors: closest_in() first");
+    if (!vox_count_) return;
+    if (points) d_map_nn_.download(points, vox_count_ * 24);
+    if (dist_sq) d_map_d2_.download(dist_sq, vox_count_ * 8);
 }
 
 double* DeviceFrameBatch::voxels_device() { return vox_made_ ? static_cast<double*>(d_vox_pts_.data()) : nullptr; }

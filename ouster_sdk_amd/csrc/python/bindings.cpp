@@ -924,6 +924,90 @@ PYBIND11_MODULE(core, m) {
             py::arg("points"), py::arg("normals"), py::arg("voxel_size"));
     }
 
+    // VoxelHashMap3d: the surface, argument names and defaults of the reference's binding (python/src/cpp/client/processing.cpp),
+    // its messages as ValueError.  get_closest_neighbors, reserve, the counters and the `host` keyword are project extensions.
+    {
+        namespace oc = ouster::sdk::core;
+        using darr = py::array_t<double, py::array::c_style | py::array::forcecast>;
+        using Map = oc::VoxelHashMap3d;
+        auto point_of = [](const darr& point) {
+            if (point.ndim() != 1 || point.shape(0) != 3) throw std::invalid_argument("VoxelHashMap method expects a 3-element point");
+            return Map::point_type{point.data()[0], point.data()[1], point.data()[2]};
+        };
+        auto to_numpy = [](const oc::ArrayX3dR& a) {
+            py::array_t<double> out({static_cast<py::ssize_t>(a.rows()), py::ssize_t(3)});
+            if (a.rows()) std::memcpy(out.mutable_data(), a.data(), a.rows() * 24);
+            return out;
+        };
+        py::class_<Map>(m, "VoxelHashMap3d")
+            .def(py::init([](double voxel_size, double max_distance, size_t max_points, size_t min_pts, bool host) {
+                     return host ? Map::on_host(voxel_size, max_distance, max_points, min_pts) : Map(voxel_size, max_distance, max_points, min_pts);
+                 }),
+                 py::arg("voxel_size") = 0.1, py::arg("max_distance") = 100.0, py::arg("max_points_per_voxel") = size_t{20},
+                 py::arg("min_pts_threshold") = size_t{1}, py::kw_only(), py::arg("host") = false)
+            .def_property_readonly("empty", &Map::empty)
+            .def("clear", &Map::clear)
+            .def(
+                "add_points",
+                [](Map& self, const darr& points) {
+                    if (points.ndim() != 2 || points.shape(1) != 3) throw std::invalid_argument("add_points expects an Nx3 array");
+                    self.add_points_array(points.data(), static_cast<size_t>(points.shape(0)));
+                },
+                py::arg("points"))
+            .def(
+                "update",
+                [point_of](Map& self, const darr& points, const darr& position) {
+                    if (points.ndim() != 2 || points.shape(1) != 3) throw std::invalid_argument("add_points expects an Nx3 array");
+                    oc::ArrayX3dR rows(static_cast<size_t>(points.shape(0)));
+                    if (rows.rows()) std::memcpy(rows.data(), points.data(), rows.rows() * 24);
+                    self.update(rows, point_of(position));
+                },
+                py::arg("points"), py::arg("position"))
+            .def("point_cloud", [to_numpy](const Map& self) { return to_numpy(self.pointcloud()); })
+            .def(
+                "remove_voxels_far_from_location", [point_of](Map& self, const darr& point) { self.remove_voxels_far_from_location(point_of(point)); },
+                py::arg("point"))
+            .def(
+                "extract_voxels_far_from_location",
+                [point_of, to_numpy](Map& self, const darr& point) { return to_numpy(self.extract_voxels_far_from_location(point_of(point))); },
+                py::arg("point"))
+            .def(
+                "get_closest_neighbor",
+                [point_of](const Map& self, const darr& point, double max_distance_sq) {
+                    const auto r = self.get_closest_neighbor(point_of(point), max_distance_sq);
+                    py::array_t<double> p(py::ssize_t(3));
+                    std::memcpy(p.mutable_data(), std::get<0>(r).data(), 24);
+                    return py::make_tuple(p, std::get<1>(r));
+                },
+                py::arg("point"), py::arg("max_distance_sq") = std::numeric_limits<double>::max())
+            .def(
+                "get_closest_neighbors",
+                [](const Map& self, const darr& queries, double max_distance_sq) {
+                    if (queries.ndim() != 2 || queries.shape(1) != 3) throw std::invalid_argument("get_closest_neighbors expects an Nx3 array");
+                    const py::ssize_t q = queries.shape(0);
+                    py::array_t<double> pts({q, py::ssize_t(3)}), d2(q);
+                    double none[3];
+                    self.closest_array(queries.data(), static_cast<size_t>(q), max_distance_sq, q ? pts.mutable_data() : none,
+                                       q ? d2.mutable_data() : none);
+                    return py::make_tuple(pts, d2);
+                },
+                py::arg("queries"), py::arg("max_distance_sq") = std::numeric_limits<double>::max())
+            .def_static(
+                "point_to_voxel",
+                [point_of](const darr& point, double inv_voxel_size) {
+                    const auto v = Map::point_to_voxel(point_of(point), inv_voxel_size);
+                    return py::make_tuple(v[0], v[1], v[2]);
+                },
+                py::arg("point"), py::arg("inv_voxel_size"))
+            .def("reserve", &Map::reserve, py::arg("voxels"))
+            .def_property_readonly("max_points_per_voxel", &Map::max_points_per_voxel)
+            .def_property_readonly("min_pts_threshold", &Map::min_pts_threshold)
+            .def_property_readonly("num_voxels", &Map::num_voxels)
+            .def_property_readonly("num_points", &Map::num_points)
+            .def_property_readonly("device_bytes", &Map::device_bytes)
+            .def_property_readonly("device", &Map::device);
+    }
+
     // ICP: the names, keywords and defaults of ouster.sdk.algorithm.point_to_point_align / point_to_plane_align; the reference's
     // messages as ValueError
     {

@@ -1,0 +1,132 @@
+// voxel_map_ref_main.cpp -- the plain C++ half of the voxel map (csrc/host/voxel_map_util.cpp) in a program of its own, built with
+// -fsanitize=address,undefined by tests/cpp/voxel_map.mk: validation, every operation of HostVoxelMap against a brute-force search
+// and against its own bookkeeping, at the edges of the int32 grid.  No GPU, no library.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "../../ouster_sdk_amd/csrc/voxel_map_host.h"
+
+using namespace ouster_hip_dev;
+
+int ouster_hip_dev::fail_msg(int code, const char*) { return code; }
+
+static int failures = 0;
+#define CHECK(cond)                                                 \
+    do {                                                            \
+        if (!(cond)) {                                              \
+            std::printf("FAIL line %d: %s\n", __LINE__, #cond);     \
+            ++failures;                                             \
+        }                                                           \
+    } while (0)
+
+static std::vector<double> cloud(size_t n, double scale, uint32_t seed) {
+    std::vector<double> a(3 * n);
+    uint32_t s = seed;
+    for (double& v : a) {
+        s = s * 1664525u + 1013904223u;
+        v = scale * (static_cast<double>(s >> 8) / 16777216.0 - 0.5);
+    }
+    return a;
+}
+
+int main() {
+    const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+    ouster_hip_voxel_map_desc d{};
+    d.voxel_size = 1.0, d.max_distance = 3.0, d.max_points_per_voxel = 20, d.min_pts_threshold = 1;
+    CHECK(voxel_map_validate(&d) == nullptr);
+    ouster_hip_voxel_map_desc b = d;
+    b.max_points_per_voxel = 0, b.voxel_size = 0.0;
+    CHECK(std::strcmp(voxel_map_validate(&b), "max_points_per_voxel must be greater than 0") == 0);
+    b = d, b.voxel_size = nan, b.max_distance = -1.0;
+    CHECK(std::strcmp(voxel_map_validate(&b), "voxel_size must be greater than 0") == 0);
+    b = d, b.max_distance = inf, b.num_attributes = 1;
+    CHECK(std::strcmp(voxel_map_validate(&b), "max_distance must be greater than 0") == 0);
+    b = d, b.num_attributes = 1;
+    CHECK(std::strcmp(voxel_map_validate(&b), "num_attributes must be 0 for a fixed-size PointType") == 0);
+    b = d, b.max_distance = 2147483647.0;
+    CHECK(std::strcmp(voxel_map_validate(&b), "voxel map: max_distance / voxel_size exceeds the int32 voxel grid") == 0);
+    b = d, b.max_distance = 2147483646.0;
+    CHECK(voxel_map_validate(&b) == nullptr && voxel_map_params(&b).max_voxel_dist == 2147483647);
+    const VoxelMapParams p = voxel_map_params(&d);
+    CHECK(p.max_voxel_dist == 4 && p.inv == 1.0 && p.resolution_sq == 1.0 / 20.0);
+
+    int32_t cell[3];
+    const double edge[3] = {2147483647.5, -2147483648.0, -0.0};
+    CHECK(voxel_map_cell(edge, 1.0, cell) && cell[0] == 2147483647 && cell[1] == INT32_MIN && cell[2] == 0);
+    const double out1[3] = {2147483648.0, 0, 0}, out2[3] = {0, nan, 0}, out3[3] = {0, 0, -inf};
+    CHECK(!voxel_map_cell(out1, 1.0, cell) && !voxel_map_cell(out2, 1.0, cell) && !voxel_map_cell(out3, 1.0, cell));
+    const int32_t lo[3] = {INT32_MIN, INT32_MIN, INT32_MIN}, hi[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, o[3] = {0, 0, 0};
+    const int32_t at[3] = {4, 0, 0}, near[3] = {3, 2, 1};
+    CHECK(voxel_map_far(lo, hi, 2147483647) && voxel_map_far(hi, lo, 4) && !voxel_map_far(lo, lo, 1));
+    CHECK(voxel_map_far(at, o, 4) && !voxel_map_far(near, o, 4) && !voxel_map_far(hi, o, 2147483647) == false);
+
+    HostVoxelMap m(p);
+    double pt[3], d2;
+    const double q0[3] = {0.5, 0.5, 0.5};
+    m.closest(q0, 7.0, pt, &d2);
+    CHECK(d2 == 7.0 && pt[0] == 0.0 && m.voxels() == 0);
+    const std::vector<double> a = cloud(3000, 10.0, 7u);
+    CHECK(m.add_points(a.data(), false, 3000, 3));
+    std::vector<float> af(a.begin(), a.end());
+    CHECK(m.add_points(af.data(), true, 750, 4));          // stride 4 over the same floats: other rows
+    const uint64_t voxels = m.voxels(), points = m.points();
+    CHECK(voxels > 0 && points >= voxels && points <= voxels * 20);
+    std::vector<double> bad = cloud(5, 1.0, 3u);
+    bad[13] = nan;
+    CHECK(!m.add_points(bad.data(), false, 5, 3) && m.voxels() == voxels && m.points() == points);
+    std::vector<double> held(3 * points);
+    m.pointcloud(held.data());
+    const std::vector<double> q = cloud(400, 12.0, 99u);
+    for (size_t i = 0; i < 400; ++i) {
+        double best = std::numeric_limits<double>::max();
+        for (size_t k = 0; k < points; ++k) {
+            const double dx = held[3 * k] - q[3 * i], dy = held[3 * k + 1] - q[3 * i + 1], dz = held[3 * k + 2] - q[3 * i + 2];
+            const double v = (dx * dx + dy * dy) + dz * dz;
+            if (v < best) best = v;
+        }
+        m.closest(&q[3 * i], 1.0, pt, &d2);
+        if (best < 1.0) CHECK(d2 == best);
+        else CHECK(d2 == 1.0 && pt[0] == 0.0 && pt[1] == 0.0 && pt[2] == 0.0);
+    }
+    const double qn[3] = {nan, 0, 0};
+    m.closest(qn, 2.0, pt, &d2);
+    CHECK(d2 == 2.0);
+    const int32_t origin[3] = {1, -1, 0};
+    const uint64_t far = m.count_far(origin);
+    CHECK(far > 0 && far < points);
+    std::vector<double> gone(3 * far);
+    m.remove_far(origin, gone.data());
+    CHECK(m.points() == points - far && m.count_far(origin) == 0 && m.voxels() < voxels);
+    std::vector<double> kept(3 * m.points());
+    m.pointcloud(kept.data());
+    // the survivors keep their order: `kept` is `held` without the rows of `gone`
+    size_t g = 0, k = 0;
+    for (size_t i = 0; i < points; ++i) {
+        if (k < m.points() && std::memcmp(&held[3 * i], &kept[3 * k], 24) == 0) ++k;
+        else if (g < far && std::memcmp(&held[3 * i], &gone[3 * g], 24) == 0) ++g;
+        else CHECK(false);
+    }
+    CHECK(k == m.points() && g == far);
+    m.closest(&kept[0], std::numeric_limits<double>::max(), pt, &d2);    // survivors are still found
+    CHECK(d2 == 0.0 && std::memcmp(pt, &kept[0], 24) == 0);
+    m.remove_far(origin, nullptr);                                        // nothing to do
+    CHECK(m.points() == points - far);
+    const int32_t away[3] = {INT32_MAX, INT32_MIN, 0};
+    m.remove_far(away, nullptr);
+    CHECK(m.voxels() == 0 && m.points() == 0);
+    m.reserve(100);
+    CHECK(m.capacity() >= 100 && m.add_points(a.data(), false, 10, 3) && m.points() > 0);
+    m.clear();
+    CHECK(m.voxels() == 0);
+    // the top cell of the grid: the +1 neighbours do not exist
+    const double top[6] = {2147483647.5, 0.5, 0.5, 2147483646.5, 0.5, 0.5};
+    CHECK(m.add_points(top, false, 2, 3) && m.voxels() == 2);
+    const double qt[3] = {2147483647.25, 0.5, 0.5};
+    m.closest(qt, std::numeric_limits<double>::max(), pt, &d2);
+    CHECK(pt[0] == 2147483647.5 && d2 == 0.0625);
+    std::printf(failures ? "voxel_map_ref_main: FAILED\n" : "voxel_map_ref_main: ok\n");
+    return failures ? 1 : 0;
+}
