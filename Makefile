@@ -24,7 +24,7 @@ FEATURES := image tonemap frame_ops pose normals voxel voxel_map icp
 # k_dewarp_experiments.hip holds the frame dewarp's experimental kernels and is part of an EXPERIMENTS=1 build only.
 STANDALONE := destagger cartesian dewarp osf
 HIP_OBJS := $(foreach i,$(SPEC_IDS),$(OBJ)/k_decode_$(i).o) $(foreach i,$(STREAM_IDS),$(OBJ)/k_decode_stream_$(i).o) $(STANDALONE:%=$(OBJ)/k_%.o) $(if $(EXPERIMENTS),$(OBJ)/k_dewarp_experiments.o,) $(OBJ)/k_image.o $(OBJ)/k_tonemap.o $(OBJ)/k_frame_ops.o $(OBJ)/k_pose.o $(OBJ)/pose_util.o $(OBJ)/k_normals.o $(OBJ)/normals_util.o $(OBJ)/k_voxel.o $(OBJ)/voxel_util.o $(OBJ)/k_voxel_map.o $(OBJ)/voxel_map_util.o $(OBJ)/k_icp.o $(OBJ)/icp_util.o $(OBJ)/decode_launch.o $(OBJ)/decode_plan.o $(OBJ)/standalone_plan.o $(OBJ)/ouster_hip_capi.o $(STANDALONE:%=$(OBJ)/capi_%.o) $(FEATURES:%=$(OBJ)/capi_%.o) $(OBJ)/host_pool.o
-HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/standalone_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/dwf_dev.h $(CSRC)/wide_tile.h $(CSRC)/launch_util.h $(CSRC)/lds_grant.h $(CSRC)/k_image.h $(CSRC)/k_tonemap.h $(CSRC)/tonemap_dev.h $(CSRC)/k_frame_ops.h $(CSRC)/k_pose.h $(CSRC)/pose_host.h $(CSRC)/k_normals.h $(CSRC)/normals_host.h $(CSRC)/k_voxel.h $(CSRC)/voxel_host.h $(CSRC)/voxel_dev.h $(CSRC)/k_voxel_map.h $(CSRC)/voxel_map_host.h $(CSRC)/k_icp.h $(CSRC)/icp_host.h $(CSRC)/capi_internal.h $(CSRC)/carve.h include/ouster_hip.h
+HIP_HDRS := $(CSRC)/ouster_hip_dev.h $(CSRC)/decode_plan.h $(CSRC)/decode_tuner.h $(CSRC)/standalone_plan.h $(CSRC)/host_pool.h $(CSRC)/kernels_common.h $(CSRC)/dwf_dev.h $(CSRC)/wide_tile.h $(CSRC)/launch_util.h $(CSRC)/lds_grant.h $(CSRC)/k_image.h $(CSRC)/k_tonemap.h $(CSRC)/tonemap_dev.h $(CSRC)/k_frame_ops.h $(CSRC)/k_pose.h $(CSRC)/pose_host.h $(CSRC)/k_normals.h $(CSRC)/normals_host.h $(CSRC)/k_voxel.h $(CSRC)/voxel_host.h $(CSRC)/voxel_dev.h $(CSRC)/k_voxel_map.h $(CSRC)/voxel_map_host.h $(CSRC)/k_icp.h $(CSRC)/icp_host.h $(CSRC)/capi_internal.h $(CSRC)/carve.h include/ouster_hip.h
 ROCM ?= /opt/rocm
 CXXFLAGS := -O2 -std=c++17 -fPIC -pthread -Wall -Wextra -Iinclude -I$(CSRC)/host -I$(ROCM)/include -D__HIP_PLATFORM_AMD__
 

@@ -66,10 +66,7 @@ int icp_prepare(ouster_hip_ctx* ctx, const ouster_hip_icp_desc* d, IcpCall& c) {
     a.table_mask = (uint32_t)((1ull << log2) - 1);
     HIP_TRY(icp_temp_bytes(a.n_src, a.n_tgt, &c.temp_bytes));
     const size_t total = icp_layout(nullptr, c);
-    if (ctx->icp_ws.cap < total) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->icp_ws.ensure(total)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (icp workspace, %zu bytes)", total);
-    }
+    if (const int rc = grow_idle(ctx, ctx->icp_ws, total, "icp workspace", true)) return rc;
     icp_layout(ctx->icp_ws.p, c);
     return OUSTER_HIP_OK;
 }
@@ -285,10 +282,7 @@ int icp_many_prepare(ouster_hip_ctx* ctx, const ouster_hip_icp_target* t, const 
     c.hdr.assign(n_sources, IcpHeader{});
     HIP_TRY(icp_many_temp_bytes(m.n_rows, m.n_sources, &c.temp_bytes));
     const size_t total = icp_many_layout(nullptr, c);
-    if (ctx->icp_ws.cap < total) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->icp_ws.ensure(total)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (icp workspace, %zu bytes)", total);
-    }
+    if (const int rc = grow_idle(ctx, ctx->icp_ws, total, "icp workspace", true)) return rc;
     icp_many_layout(ctx->icp_ws.p, c);
     return OUSTER_HIP_OK;
 }
@@ -401,10 +395,7 @@ int icp_one_device(ouster_hip_ctx* ctx, const ouster_hip_icp_target* t, ouster_h
         return k.total;
     };
     const size_t total = layout(nullptr);
-    if (ctx->icp_ws.cap < total) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->icp_ws.ensure(total)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (icp workspace, %zu bytes)", total);
-    }
+    if (const int rc = grow_idle(ctx, ctx->icp_ws, total, "icp workspace", true)) return rc;
     layout(ctx->icp_ws.p);
     a.slots = t->slots, a.slot_end = t->slot_end, a.sidx = t->sidx, a.rows = t->rows;
     HIP_TRY(hipMemsetAsync(a.rb, 0, sizeof(IcpReadback), ctx->stream));   // a clean header, as after the grid of a single call

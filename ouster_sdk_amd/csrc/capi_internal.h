@@ -4,13 +4,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
-#include <map>
+#include <deque>
 #include <string>
 #include <utility>
 #include <vector>
 
+#include "decode_tuner.h"
 #include "host_pool.h"
 #include "ouster_hip_dev.h"
 
@@ -31,9 +33,16 @@ int fail_msg(int code, const char* msg);
 inline size_t float_elem(int dtype) { return dtype == OUSTER_HIP_F32 ? 4 : dtype == OUSTER_HIP_F64 ? 8 : 0; }
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-struct DevBuf {
+// What the context owns frees itself: ouster_hip_ctx_destroy makes the device current, waits for the stream and deletes.
+// (HIDDEN on what is new here: the library's dynamic symbols stay what they were.)
+#define HIDDEN __attribute__((visibility("hidden")))
+struct DevBuf {   // a grow-only block of device memory
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    HIDDEN ~DevBuf() { counted_free(p); }
     int ensure(size_t n) {
         if (n <= cap) return 0;
         counted_free(p);
@@ -47,27 +56,50 @@ struct DevBuf {
         cap = want;
         return 0;
     }
-    void release() {
-        counted_free(p);
+};
+
+struct HIDDEN PinnedBuf {   // a grow-only block of page-locked host memory: at least `n` bytes, `want` of them when it grows
+    void* p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t ensure(size_t n, size_t want) {
+        if (n <= cap) return hipSuccess;
+        if (p) (void)hipHostFree(p);
         p = nullptr;
         cap = 0;
+        const hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) cap = want;
+        return e;
     }
 };
 
-// k_decode variant (64-column tiles / wide tiles of 128 or 256 columns / the persistent kernel) per workload, picked by
-// timing each candidate on the first calls: which one is faster depends on how the output planes happen to be placed
-// in HBM
-struct Tune {
-    int best = -2;  // -2: still measuring; 0: narrow; 128 / 256: wide; 1000 + tile width: the persistent kernel
-    int calls = 0;
-    bool from_cache = false;   // `best` was read from the tuning cache file, not timed by this context
-    static constexpr int ROUNDS = 4, NCAND = 5, SAMPLES = NCAND * ROUNDS;
-    hipEvent_t ev[SAMPLES][2] = {};  // up to five candidates x ROUNDS consecutive launches
-    float ms[NCAND] = {0, 0, 0, 0, 0};  // fastest warm sample of each candidate
-    void destroy() {
-        for (auto& pr : ev)
-            for (hipEvent_t& e : pr)
-                if (e) (void)hipEventDestroy(e), e = nullptr;
+struct HIDDEN Event {   // an event, created on first use
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+};
+
+// The variant tuner's samples of one workload (decode_tuner.h): a pair of events around each timed launch, polled, never
+// waited for.  ouster_hip_decode creates and records the pair of the slot the tuner hands out.
+struct HIDDEN TuneEvents {
+    Event ev[TUNE_SAMPLES][2];
+    bool landed(int n) const {
+        for (int i = 0; i < n; ++i)
+            if (hipEventQuery(ev[i][1].e) != hipSuccess) {
+                (void)hipGetLastError();
+                return false;
+            }
+        return true;
+    }
+    float ms(int i) const {
+        float t = 0;
+        return hipEventElapsedTime(&t, ev[i][0].e, ev[i][1].e) == hipSuccess ? t : 0.f;
     }
 };
 
@@ -76,6 +108,13 @@ template <int N>
 struct PhaseTimer {
     bool on = false, timed = false;
     hipEvent_t ev[N] = {};
+    PhaseTimer() = default;
+    PhaseTimer(const PhaseTimer&) = delete;
+    PhaseTimer& operator=(const PhaseTimer&) = delete;
+    HIDDEN ~PhaseTimer() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
     int enable(int device, bool want) {
         HIP_TRY(hipSetDevice(device));
         if (want)
@@ -85,16 +124,13 @@ struct PhaseTimer {
         timed = false;
         return OUSTER_HIP_OK;
     }
-    void destroy() {
-        for (hipEvent_t& e : ev)
-            if (e) (void)hipEventDestroy(e), e = nullptr;
-    }
 };
 
 }  // namespace ouster_hip_dev
 
 struct ouster_hip_ctx {
     using DevBuf = ouster_hip_dev::DevBuf;
+    HIDDEN ouster_hip_ctx() = default;
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -102,9 +138,8 @@ struct ouster_hip_ctx {
     DevBuf image_mask;                   // ouster_hip_image_dark_rows: the column masks of a batch
     DevBuf tonemap_ws;                   // ouster_hip_image_tonemap: tile histograms and look-up tables, 2 x 256 KB per image
     DevBuf tables;                       // upload_table: the small host table of the call in flight (shifts, row indices, pose segments, ...)
-    void* table_pin = nullptr;           //   ... its page-locked staging, and the event behind its last copy
-    size_t table_pin_cap = 0;
-    hipEvent_t table_ev = nullptr;
+    ouster_hip_dev::PinnedBuf table_pin; //   ... its page-locked staging, and the event behind its last copy
+    ouster_hip_dev::Event table_ev;
     DevBuf normals_pairs;                // ouster_hip_normals: what k_normals_subtent leaves, 16 bytes per frame and return
     ouster_hip_dev::PhaseTimer<OUSTER_HIP_VOXEL_PHASES + 1> voxel_timer;
     DevBuf voxel_ws;                     // ouster_hip_voxel_downsample: keys, table, ids, sorted indices, gathered rows, sort temporaries
@@ -122,19 +157,15 @@ struct ouster_hip_ctx {
     std::vector<ouster_hip_dev::LutDev> luts_host;   // cache key of `luts`
     // pageable host packet_counts go through a small pinned ring (no stream synchronisation)
     static constexpr int RING = 4;
-    uint32_t* ring_buf[RING] = {nullptr, nullptr, nullptr, nullptr};
-    size_t ring_cap[RING] = {0, 0, 0, 0};
-    hipEvent_t ring_ev[RING] = {nullptr, nullptr, nullptr, nullptr};
+    ouster_hip_dev::PinnedBuf ring_buf[RING];
+    ouster_hip_dev::Event ring_ev[RING];   // behind the last copy out of each
     int ring_next = 0;
     ouster_hip_dev::Knobs knobs;
     bool timing = false;
     uint32_t timing_every = 1, timing_calls = 0;   // HIP events around every timing_every-th decode kernel (an event record costs the stream 2 - 3 us)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::deque<std::array<ouster_hip_dev::Event, 2>> ev_pool;   // (a deque: the events stay where they are)
     size_t ev_used = 0;
-    std::map<uint64_t, ouster_hip_dev::Tune> tune;   // the variant tuner, by workload key (decode_plan.h)
-    // verdicts of earlier processes (ouster_hip_ctx_set_tuning_cache): workload key -> chosen variant, for THIS device and library
-    std::string tune_cache_path, tune_cache_id;
-    std::map<uint64_t, int> tune_cache;
+    ouster_hip_dev::DecodeTuner<ouster_hip_dev::TuneEvents> tuner;   // the variant tuner and its cache file (decode_tuner.h)
     const char* last_tuner = "none";     // how the last ouster_hip_decode chose its variant
     int last_tile_cols = 0, last_tile_rows = 0;  // tile of the last k_decode launch
 };
@@ -167,26 +198,27 @@ namespace ouster_hip_dev {
 __attribute__((visibility("hidden"))) int ensure_luts(ouster_hip_ctx* c, const std::vector<LutDev>& l);
 __attribute__((visibility("hidden"))) int stage_offsets(ouster_hip_ctx* c, const int32_t* shifts, uint32_t h, uint32_t w, int inverse, const int32_t** out);
 
+// `buf` holds at least `bytes`, growing only on an idle stream: a call in flight may still use the old block.  `what` is the
+// noun of the error message, which names the size too where `say_bytes`.
+HIDDEN inline int grow_idle(ouster_hip_ctx* ctx, DevBuf& buf, size_t bytes, const char* what, bool say_bytes = false) {
+    if (bytes <= buf.cap) return OUSTER_HIP_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (!buf.ensure(bytes)) return OUSTER_HIP_OK;
+    return say_bytes ? fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (%s, %zu bytes)", what, bytes)
+                     : fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (%s)", what);
+}
+
 // A small host table -> ctx->tables, safe by construction for back-to-back asynchronous calls: the source is copied into
 // page-locked staging owned by the context, the staging is reused only after the event behind its last copy has completed,
 // and the device buffer grows only on an idle stream.
 inline int upload_table(ouster_hip_ctx* ctx, const void* src, size_t bytes) {
-    if (ctx->table_ev) HIP_TRY(hipEventSynchronize(ctx->table_ev));
-    else HIP_TRY(hipEventCreateWithFlags(&ctx->table_ev, hipEventDisableTiming));
-    if (bytes > ctx->table_pin_cap) {
-        if (ctx->table_pin) (void)hipHostFree(ctx->table_pin);
-        ctx->table_pin = nullptr;
-        ctx->table_pin_cap = 0;
-        HIP_TRY(hipHostMalloc(&ctx->table_pin, bytes * 2, hipHostMallocDefault));
-        ctx->table_pin_cap = bytes * 2;
-    }
-    if (bytes > ctx->tables.cap) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));   // a kernel in flight may still read the old table
-        if (ctx->tables.ensure(bytes)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (frame_ops tables)");
-    }
-    std::memcpy(ctx->table_pin, src, bytes);
-    HIP_TRY(hipMemcpyAsync(ctx->tables.p, ctx->table_pin, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->table_ev, ctx->stream));
+    if (ctx->table_ev.e) HIP_TRY(hipEventSynchronize(ctx->table_ev.e));
+    else HIP_TRY(ctx->table_ev.create(hipEventDisableTiming));
+    HIP_TRY(ctx->table_pin.ensure(bytes, bytes * 2));
+    if (const int rc = grow_idle(ctx, ctx->tables, bytes, "frame_ops tables")) return rc;
+    std::memcpy(ctx->table_pin.p, src, bytes);
+    HIP_TRY(hipMemcpyAsync(ctx->tables.p, ctx->table_pin.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->table_ev.e, ctx->stream));
     return OUSTER_HIP_OK;
 }
 

@@ -67,10 +67,7 @@ int normals_device(ouster_hip_ctx* ctx, const ouster_hip_normals_desc* d) {
     a.consts = (const double*)ctx->tables.p;
     a.s2b = mbytes ? (const double*)((const uint8_t*)ctx->tables.p + cbytes) : nullptr;
     a.shifts = sbytes ? (const uint32_t*)((const uint8_t*)ctx->tables.p + cbytes + mbytes) : nullptr;
-    if (ctx->normals_pairs.cap < rows * sizeof(NormalsPair)) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->normals_pairs.ensure(rows * sizeof(NormalsPair))) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (normals)");
-    }
+    if (const int rc = grow_idle(ctx, ctx->normals_pairs, rows * sizeof(NormalsPair), "normals")) return rc;
     a.pairs = (NormalsPair*)ctx->normals_pairs.p;
     HIP_TRY(launch_normals_subtent(a, ctx->stream));
     std::vector<NormalsPair> pairs(rows);

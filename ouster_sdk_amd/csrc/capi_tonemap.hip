@@ -84,8 +84,7 @@ int ouster_hip_image_tonemap(ouster_hip_ctx* ctx, const void* images, int in_typ
     if (!ctx) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t table = (size_t)n_images * TM_LUT_ELEMS * 4;
-    if (ctx->tonemap_ws.cap < 2 * table) HIP_TRY(hipStreamSynchronize(ctx->stream));   // a call in flight may still use the old workspace
-    if (ctx->tonemap_ws.ensure(2 * table)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (tone-map tables)");
+    if (const int rc = grow_idle(ctx, ctx->tonemap_ws, 2 * table, "tone-map tables")) return rc;
     a.hist = (uint32_t*)ctx->tonemap_ws.p;
     a.luts = (float*)((uint8_t*)ctx->tonemap_ws.p + table);
     a.params = params;

@@ -62,10 +62,7 @@ int voxel_device(ouster_hip_ctx* ctx, const ouster_hip_voxel_desc* d, uint64_t* 
     HIP_TRY(voxel_temp_bytes(a.n, &temp_bytes));
     void* temp = nullptr;
     const size_t total = voxel_layout(nullptr, a, temp_bytes, &temp);
-    if (ctx->voxel_ws.cap < total) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->voxel_ws.ensure(total)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (voxel workspace, %zu bytes)", total);
-    }
+    if (const int rc = grow_idle(ctx, ctx->voxel_ws, total, "voxel workspace", true)) return rc;
     voxel_layout(ctx->voxel_ws.p, a, temp_bytes, &temp);
     ctx->voxel_timer.timed = false;
     HIP_TRY(voxel_run(a, temp, temp_bytes, ctx->stream, ctx->voxel_timer.on ? ctx->voxel_timer.ev : nullptr));

@@ -54,10 +54,7 @@ template <class F>
 int workspace(ouster_hip_ctx* ctx, F&& carve) {
     Carver measure(nullptr);
     carve(measure);
-    if (ctx->voxel_ws.cap < measure.total) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->voxel_ws.ensure(measure.total)) return fail(OUSTER_HIP_ERR_RUNTIME, "out of device memory (voxel workspace, %zu bytes)", measure.total);
-    }
+    if (const int rc = grow_idle(ctx, ctx->voxel_ws, measure.total, "voxel workspace", true)) return rc;
     Carver c(ctx->voxel_ws.p);
     carve(c);
     return OUSTER_HIP_OK;

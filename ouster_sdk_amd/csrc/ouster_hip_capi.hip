@@ -1,6 +1,7 @@
 // ouster_hip_capi.hip -- host side of the C ABI declared in include/ouster_hip.h.
-// Owns the error channel and the context (stream, scratch, knobs, tuning cache), turns format descriptions into the decode's
-// tables, and runs the fused decode: the variant tuner, the launch plan (decode_plan.cpp) and the launches of k_decode*.hip.
+// Owns the error channel and the context (stream, scratch, knobs), turns format descriptions into the decode's tables, and
+// runs the fused decode: the variant tuner's choice (decode_tuner.h; here only the events of the launches it wants timed), the
+// launch plan (decode_plan.cpp) and the launches of k_decode*.hip.
 // Every other entry point is in capi_<feature>.hip, next to the feature's kernels (destagger, cartesian and the LUTs, dewarp,
 // OSF, images, frame_ops, pose, normals, voxel, ICP).
 #include <hip/hip_runtime.h>
@@ -8,9 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <fcntl.h>
 #include <new>
-#include <unistd.h>
 
 #include "capi_internal.h"
 
@@ -31,11 +30,6 @@ int fail(int code, const char* fmt, ...) {
 // the error channel of the plain C++ parts of the library (csrc/pose_host.h)
 int fail_msg(int code, const char* msg) { return fail(code, "%s", msg); }
 }  // namespace ouster_hip_dev
-
-static void tune_forget(ouster_hip_ctx* c) {   // the one place the tuner's events are destroyed
-    for (auto& kv : c->tune) kv.second.destroy();
-    c->tune.clear();
-}
 
 static void fill_geometry(const ouster_hip_format_desc& d, Geometry& g) {
     g.pixels_per_column = d.pixels_per_column;
@@ -109,37 +103,8 @@ void ouster_hip_ctx_destroy(ouster_hip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->state.release();
-    c->tile_valid.release();
-    for (int i = 0; i < ouster_hip_ctx::RING; ++i) {
-        if (c->ring_buf[i]) (void)hipHostFree(c->ring_buf[i]);
-        if (c->ring_ev[i]) (void)hipEventDestroy(c->ring_ev[i]);
-    }
-    c->offsets.release();
-    c->luts.release();
-    c->counts.release();
-    c->scratch.release();
-    c->slotmap.release();
-    c->hdrw.release();
-    c->osf_pixels.release();
-    c->image_mask.release();
-    c->tonemap_ws.release();
-    c->tables.release();
-    c->normals_pairs.release();
-    c->voxel_ws.release();
-    c->icp_ws.release();
-    c->icp_timer.destroy();
-    c->voxel_timer.destroy();
-    if (c->table_ev) (void)hipEventDestroy(c->table_ev);
-    if (c->table_pin) (void)hipHostFree(c->table_pin);
-    for (auto& b : c->user_scratch) b.release();
-    for (auto& p : c->ev_pool) {
-        (void)hipEventDestroy(p.first);
-        (void)hipEventDestroy(p.second);
-    }
-    tune_forget(c);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // every member frees what it owns (capi_internal.h), the device still current
 }
 
 void* ouster_hip_ctx_stream(ouster_hip_ctx* c) { return c ? (void*)c->stream : nullptr; }
@@ -151,8 +116,7 @@ int ouster_hip_ctx_set_knob(ouster_hip_ctx* c, const char* name, int value) {
     if (!strcmp(name, "retune")) {   // forget what the variant tuner learnt (the caller moved its buffers: pick_placement)
         if (value) {
             (void)hipStreamSynchronize(c->stream);
-            tune_forget(c);
-            c->tune_cache.clear();   // what this context read from the cache file is void as well: it re-measures and appends anew
+            c->tuner.forget();   // what this context read from the cache file is void as well: it re-measures and appends anew
         }
         return OUSTER_HIP_OK;
     }
@@ -162,45 +126,21 @@ int ouster_hip_ctx_set_knob(ouster_hip_ctx* c, const char* name, int value) {
     return OUSTER_HIP_OK;
 }
 
-// ---- persisted verdicts of the variant tuner -----------------------------------------------------------------------------
-// One text line per verdict: "v1 <device and library id> <workload key, hex> <variant> <its fastest sample, ms>".  Lines are
-// appended with one write() each (O_APPEND: ranks of one job may share the file), the last line of a key wins at load.
+// persisted verdicts of the variant tuner (decode_tuner.h), under the id of this device and library
 int ouster_hip_ctx_set_tuning_cache(ouster_hip_ctx* c, const char* path) {
     if (!c) return fail(OUSTER_HIP_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    c->tune_cache.clear();
-    c->tune_cache_path = path ? path : "";
-    if (c->tune_cache_path.empty()) return OUSTER_HIP_OK;
-    hipDeviceProp_t prop{};
-    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) {
-        (void)hipGetLastError();
-        c->tune_cache_path.clear();
-        return fail(OUSTER_HIP_ERR_RUNTIME, "hipGetDeviceProperties failed");
+    std::string id;
+    if (path && *path) {
+        hipDeviceProp_t prop{};
+        if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) {
+            (void)hipGetLastError();
+            c->tuner.set_cache("", "");
+            return fail(OUSTER_HIP_ERR_RUNTIME, "hipGetDeviceProperties failed");
+        }
+        id = tune_cache_id(prop.gcnArchName, prop.multiProcessorCount, prop.name, ouster_hip_version());
     }
-    std::string id = std::string(prop.gcnArchName) + ":" + std::to_string(prop.multiProcessorCount) + ":" + prop.name + ":" + ouster_hip_version();
-    for (char& ch : id) if (ch == ' ' || ch == '\t') ch = '_';
-    c->tune_cache_id = id;
-    if (FILE* f = fopen(c->tune_cache_path.c_str(), "r")) {
-        char line[512], ver[8], dev[320];
-        unsigned long long key = 0;
-        int best = 0;
-        float ms = 0;
-        while (fgets(line, sizeof line, f))
-            if (sscanf(line, "%7s %319s %llx %d %f", ver, dev, &key, &best, &ms) == 5 && !strcmp(ver, "v1") && id == dev)
-                c->tune_cache[(uint64_t)key] = best;
-        fclose(f);
-    }
+    c->tuner.set_cache(path ? path : "", id);
     return OUSTER_HIP_OK;
-}
-static void tune_cache_append(ouster_hip_ctx* c, uint64_t key, int best, float ms) {
-    if (c->tune_cache_path.empty()) return;
-    c->tune_cache[key] = best;
-    char line[512];
-    const int n = snprintf(line, sizeof line, "v1 %s %016llx %d %.4f\n", c->tune_cache_id.c_str(), (unsigned long long)key, best, ms);
-    if (n <= 0 || n >= (int)sizeof line) return;
-    const int fd = open(c->tune_cache_path.c_str(), O_WRONLY | O_APPEND | O_CREAT, 0644);
-    if (fd < 0) return;   // a cache that cannot be written is not an error of the decode
-    (void)!write(fd, line, (size_t)n);
-    close(fd);
 }
 const char* ouster_hip_last_decode_tuner(ouster_hip_ctx* c) { return c ? c->last_tuner : ""; }
 
@@ -355,87 +295,20 @@ static int stage_counts(ouster_hip_ctx* ctx, const uint32_t* packet_counts, uint
     if (!pinned) {
         slot = ctx->ring_next;
         ctx->ring_next = (slot + 1) % ouster_hip_ctx::RING;
-        if (!ctx->ring_ev[slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->ring_ev[slot], hipEventDisableTiming));
-        else HIP_TRY(hipEventSynchronize(ctx->ring_ev[slot]));  // RING calls ago: long done
-        if (ctx->ring_cap[slot] < bytes) {
-            if (ctx->ring_buf[slot]) (void)hipHostFree(ctx->ring_buf[slot]);
-            ctx->ring_buf[slot] = nullptr;
-            ctx->ring_cap[slot] = 0;
-            HIP_TRY(hipHostMalloc((void**)&ctx->ring_buf[slot], bytes + bytes / 2, hipHostMallocDefault));
-            ctx->ring_cap[slot] = bytes + bytes / 2;
-        }
-        memcpy(ctx->ring_buf[slot], packet_counts, bytes);
-        src = ctx->ring_buf[slot];
+        if (!ctx->ring_ev[slot].e) HIP_TRY(ctx->ring_ev[slot].create(hipEventDisableTiming));
+        else HIP_TRY(hipEventSynchronize(ctx->ring_ev[slot].e));  // RING calls ago: long done
+        HIP_TRY(ctx->ring_buf[slot].ensure(bytes, bytes + bytes / 2));
+        memcpy(ctx->ring_buf[slot].p, packet_counts, bytes);
+        src = ctx->ring_buf[slot].p;
     }
     HIP_TRY(hipMemcpyAsync(ctx->counts.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (slot >= 0) HIP_TRY(hipEventRecord(ctx->ring_ev[slot], ctx->stream));
+    if (slot >= 0) HIP_TRY(hipEventRecord(ctx->ring_ev[slot].e, ctx->stream));
     *d_counts = (const uint32_t*)ctx->counts.p;
     return OUSTER_HIP_OK;
 }
 
 static bool fast_possible(const Knobs& kn, uint32_t slots_per_frame, const Geometry& g) {
     return kn.fast && (uint64_t)slots_per_frame * g.columns_per_packet == g.columns_per_frame;
-}
-
-// ---- the variant tuner ----------------------------------------------------------------------------
-// Four launches of each candidate, back to back (a launch that follows a different variant is not representative of the
-// steady state: alternating the candidates made the 64-column kernel look 8 % faster than it then ran).  Single launches
-// vary by ~10 %, mostly upwards, and the candidates can be within 1-5 % of each other: each candidate's fastest sample
-// counts, its first one (cold code, cold TLB, another variant's write-backs still draining) only when nothing else landed.
-// The clocks are polled, never waited for: until all samples have landed the default variant runs.
-// every sample of `t` is queued: once all have landed, the fastest candidate becomes the verdict (and goes to the cache file)
-static void tune_collect(ouster_hip_ctx* c, uint64_t key, Tune& t, const int* cand, int nc) {
-    constexpr int R = Tune::ROUNDS;
-    const int NS = nc * R;
-    for (int i = 0; i < NS; ++i)
-        if (hipEventQuery(t.ev[i][1]) != hipSuccess) {
-            (void)hipGetLastError();
-            return;
-        }
-    float cold[Tune::NCAND] = {0, 0, 0, 0, 0};
-    for (int i = 0; i < NS; ++i) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, t.ev[i][0], t.ev[i][1]) != hipSuccess || ms <= 0) continue;
-        float& slot = (i % R == 0) ? cold[i / R] : t.ms[i / R];
-        if (slot == 0 || ms < slot) slot = ms;
-    }
-    for (int k = 0; k < nc; ++k)
-        if (t.ms[k] == 0) t.ms[k] = cold[k];
-    t.best = 256;
-    float best_ms = 0;
-    for (int k = 0; k < nc; ++k)
-        if (t.ms[k] > 0 && (best_ms == 0 || t.ms[k] < best_ms)) { t.best = cand[k]; best_ms = t.ms[k]; }
-    tune_cache_append(c, key, t.best, best_ms);
-}
-
-// What this call launches: a verdict (measured, or an earlier process's from the cache file), the next sample of a
-// candidate (then `record` / `slot` say where its two events go), or the default variant while samples are in flight.
-struct TuneStep {
-    int variant;
-    Tune* record;
-    int slot;
-};
-static TuneStep tune_step(ouster_hip_ctx* c, uint64_t key, const int* cand, int nc) {
-    if (c->tune.size() > 64 && !c->tune.count(key)) tune_forget(c);   // bounded: forget everything, re-learn
-    const bool fresh = !c->tune.count(key);
-    Tune& t = c->tune[key];
-    if (fresh) {   // an earlier process (or rank) has timed this workload on this device: launch its choice from call 1
-        auto hit = c->tune_cache.find(key);
-        if (hit != c->tune_cache.end() && std::find(cand, cand + nc, hit->second) != cand + nc) {
-            t.best = hit->second;
-            t.from_cache = true;
-        }
-    }
-    const int NS = nc * Tune::ROUNDS;
-    if (t.best == -2 && t.calls >= NS) tune_collect(c, key, t, cand, nc);
-    if (t.best != -2) {
-        c->last_tuner = t.from_cache ? "cache" : "measured";
-        return {t.best, nullptr, -1};
-    }
-    c->last_tuner = "measuring";
-    if (t.calls >= NS) return {256, nullptr, -1};   // every sample is queued, not all have landed
-    const int slot = t.calls++;
-    return {cand[slot / Tune::ROUNDS], &t, slot};
 }
 
 // ---- decode: the steps of ouster_hip_decode, in its order -----------------------------------------------------------------
@@ -607,6 +480,51 @@ static int fill_decode_args(DecodeArgs& da, ouster_hip_ctx* ctx, const ouster_hi
     return spec;
 }
 
+// what the launch plan (decode_plan.h) is a function of
+static PlanInput fill_plan_input(const DecodeArgs& da, const ouster_hip_ctx* ctx, int spec, int xyzm) {
+    PlanInput in{};
+    in.g = da.g;
+    in.kn = ctx->knobs;
+    in.n_frames = da.n_frames;
+    in.slots_per_frame = da.slots_per_frame;
+    in.packet_stride = da.packet_stride;
+    in.packets = (uintptr_t)da.packets;
+    in.xyz_poses = (uintptr_t)da.xyz_poses;
+    in.spec = spec;
+    in.xyzm = xyzm;
+    in.vec_ok = da.vec_ok;
+    in.n_fields = da.n_fields;
+    for (uint32_t i = 0; i < da.n_fields; ++i) {
+        in.plane_mask |= da.planes[i] ? (1ull << i) : 0;
+        in.destagger_mask |= da.destaggered[i] ? (1ull << i) : 0;
+    }
+    in.xyz_mask = (da.xyz[0] ? 1u : 0u) | (da.xyz[1] ? 2u : 0u);
+    in.gate_counts = da.gate_counts != nullptr;
+    in.host_ts = da.host_timestamps && da.packet_timestamp;
+    in.cus = ctx->cus;
+    in.resident_wgs = ctx->resident_wgs;
+#ifdef OUSTER_EXPERIMENTS
+    in.may_resolve = true;
+#else
+    in.may_resolve = false;   // k_decode_wide_resolved is not compiled
+#endif
+    return in;
+}
+
+// The variant this call launches (decode_tuner.h).  The tuner stands down with tune = 0, for a shape with nothing to choose
+// (or a choice forced by a knob) and while the stream is being captured: the default variant runs.
+using Tuner = decltype(ouster_hip_ctx::tuner);
+static Tuner::Step tune_step(ouster_hip_ctx* ctx, const PlanInput& in, const Candidates& cand) {
+    Tuner::Step ts;
+    if (cand.n && in.kn.tune) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(ctx->stream, &cap);
+        if (cap == hipStreamCaptureStatusNone) ts = ctx->tuner.step(tuner_key(in, cand), cand.variant, cand.n);
+    }
+    ctx->last_tuner = ts.source;
+    return ts;
+}
+
 static void set_shape(DecodeArgs& da, const TileShape& s) {
     da.rows_per_tile = s.rows_per_tile;
     da.row_chunks = s.row_chunks;
@@ -653,42 +571,10 @@ int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const u
 #endif
 
     // ---- the plan (decode_plan.h): which kernel, which tiles, which scratch
-    PlanInput in{};
-    in.g = g;
-    in.kn = ctx->knobs;
-    in.n_frames = n_frames;
-    in.slots_per_frame = slots_per_frame;
-    in.packet_stride = packet_stride;
-    in.packets = (uintptr_t)packets;
-    in.xyz_poses = (uintptr_t)da.xyz_poses;
-    in.spec = spec;
-    in.xyzm = xyzm;
-    in.vec_ok = da.vec_ok;
-    in.n_fields = nf;
-    for (uint32_t i = 0; i < nf; ++i) {
-        in.plane_mask |= da.planes[i] ? (1ull << i) : 0;
-        in.destagger_mask |= da.destaggered[i] ? (1ull << i) : 0;
-    }
-    in.xyz_mask = (da.xyz[0] ? 1u : 0u) | (da.xyz[1] ? 2u : 0u);
-    in.gate_counts = out->gate_counts != nullptr;
-    in.host_ts = da.host_timestamps && da.packet_timestamp;
-    in.cus = ctx->cus;
-    in.resident_wgs = ctx->resident_wgs;
-#ifdef OUSTER_EXPERIMENTS
-    in.may_resolve = true;
-#else
-    in.may_resolve = false;   // k_decode_wide_resolved is not compiled
-#endif
+    const PlanInput in = fill_plan_input(da, ctx, spec, xyzm);
     const bool fast = fast_possible(in.kn, slots_per_frame, g);
     const Candidates cand = plan_candidates(in);
-    // the tuner stands down with tune = 0 and while the stream is being captured: the default variant runs
-    TuneStep ts{256, nullptr, -1};
-    ctx->last_tuner = "none";   // forced by a knob, or a shape with nothing to choose
-    if (cand.n && in.kn.tune) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(st, &cap);
-        if (cap == hipStreamCaptureStatusNone) ts = tune_step(ctx, tuner_key(in, cand), cand.variant, cand.n);
-    }
+    const Tuner::Step ts = tune_step(ctx, in, cand);
     DecodePlan plan = plan_decode(in, cand, ts.variant);
     if (!plan.ok)   // the general mapping keeps resolve_frame's scratch ((2 + cpp) words per buffer slot) in LDS next to the tile
         return fail(OUSTER_HIP_ERR_UNSUPPORTED,
@@ -718,21 +604,18 @@ int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const u
     // ---- the optimistic (or only) pass
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (ctx->timing && (ctx->timing_calls++ % ctx->timing_every) == 0) {
-        if (ctx->ev_used == ctx->ev_pool.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            ctx->ev_pool.emplace_back(a, b);
-        }
-        e0 = ctx->ev_pool[ctx->ev_used].first;
-        e1 = ctx->ev_pool[ctx->ev_used].second;
+        if (ctx->ev_used == ctx->ev_pool.size()) ctx->ev_pool.emplace_back();
+        auto& pair = ctx->ev_pool[ctx->ev_used];
+        for (Event& e : pair) HIP_TRY(e.create());
+        e0 = pair[0].e;
+        e1 = pair[1].e;
         ctx->ev_used++;
         HIP_TRY(hipEventRecord(e0, st));
     }
-    if (ts.record) {
-        for (int k = 0; k < 2; ++k)
-            if (!ts.record->ev[ts.slot][k]) HIP_TRY(hipEventCreate(&ts.record->ev[ts.slot][k]));
-        HIP_TRY(hipEventRecord(ts.record->ev[ts.slot][0], st));
+    Event* const sample = ts.record ? ts.record->ev[ts.slot] : nullptr;   // the tuner wants this launch timed
+    if (sample) {
+        for (int k = 0; k < 2; ++k) HIP_TRY(sample[k].create());
+        HIP_TRY(hipEventRecord(sample[0].e, st));
     }
     if (plan.slotmap) HIP_TRY(launch_slotmap(da, ctx->device, st));
     switch (plan.kernel) {
@@ -753,7 +636,7 @@ int ouster_hip_decode(ouster_hip_ctx* ctx, const ouster_hip_format* fmt, const u
     }
     ctx->last_tile_cols = plan.cols;
     ctx->last_kernel = kernel_name(plan.kernel);
-    if (ts.record) HIP_TRY(hipEventRecord(ts.record->ev[ts.slot][1], st));
+    if (sample) HIP_TRY(hipEventRecord(sample[1].e, st));
     if (e1) HIP_TRY(hipEventRecord(e1, st));
 
     // ---- the fix-up pass: always launched behind an optimistic kernel; the workgroups of a clean batch leave after two
@@ -836,7 +719,7 @@ int ouster_hip_timing_read(ouster_hip_ctx* ctx, double* avg_ms, uint32_t* n_laun
     double total = 0;
     for (size_t i = 0; i < ctx->ev_used; ++i) {
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_pool[i].first, ctx->ev_pool[i].second));
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_pool[i][0].e, ctx->ev_pool[i][1].e));
         total += ms;
     }
     *avg_ms = ctx->ev_used ? total / (double)ctx->ev_used : 0.0;
