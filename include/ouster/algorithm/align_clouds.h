@@ -24,9 +24,6 @@
 
 namespace ouster {
 namespace sdk {
-namespace core {
-using Matrix4dR = mat4d;   ///< typedefs.h of the reference: a row-major 4x4 of double
-}  // namespace core
 
 namespace algorithm {
 

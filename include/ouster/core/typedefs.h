@@ -510,6 +510,7 @@ struct mat4d {
     }
     bool operator==(const mat4d& o) const { return std::memcmp(m, o.m, sizeof m) == 0; }
 };
+using Matrix4dR = mat4d;   ///< typedefs.h of the reference: a row-major 4x4 of double
 
 }  // namespace core
 }  // namespace sdk

@@ -20,6 +20,7 @@
 #include "ouster/core/xyzlut.h"
 #include "ouster/hip/context.h"
 #include "ouster/hip/device_buffer.h"
+#include "ouster/mapping/icp_registration.h"
 
 struct ouster_hip_format;
 
@@ -326,6 +327,11 @@ class DeviceFrameBatch {
     /** Copy them to the host (voxel_count() x 3 and voxel_count() doubles; null pointers are skipped; synchronous).
      *  @throw std::invalid_argument before closest_in() */
     void download_map_neighbors(double* points, double* dist_sq);
+    /** registration.align_points_to_map over the rows of the last voxel_downsample*(), which stay in HBM (mapping/icp_registration.h;
+     *  csrc/k_registration.hip): bit-identical to ouster_hip_registration_align on download_voxels()'s rows.  Throws as above, and
+     *  what the registration refuses (std::invalid_argument). */
+    core::Matrix4dR align_voxels_to_map(const core::VoxelHashMap3d& map, const mapping::ICPRegistration& registration, double max_distance,
+                                        double kernel_scale);
 
     /** Per-column body_to_world poses of one frame (w x 16 doubles, row-major 4x4 each; identity
      *  until set), the input of dewarp(). */

@@ -1028,6 +1028,70 @@ int ouster_hip_voxel_map_closest(const ouster_hip_voxel_map* map, const void* qu
 int ouster_hip_voxel_map_closest_host(const ouster_hip_voxel_map* map, const void* queries, int32_t dtype, uint64_t q,
                                       uint64_t row_stride, double max_distance_sq, double* out_points, double* out_dist_sq);
 
+/* ---- ICPRegistration: a cloud aligned to the resident voxel map (mapping::ICPRegistration::align_points_to_map of the reference,
+ * ouster_mapping/src/icp_registration.cpp), held to tests/registration_model.py.  A pass is one kernel (k_registration.hip,
+ * k_reg_pass): a workgroup of 256 threads owns ouster_hip_icp_chunk_rows() rows; a thread applies the previous pass's estimate to
+ * its rows (the moved cloud lives in the context's workspace, 24 bytes a row, and keeps the roundings of every earlier pass), asks
+ * the map with the body of ouster_hip_voxel_map_closest, and forms the Geman-McClure weight k^2 / (k + r2)^2 and the 16 terms of the
+ * 6 x 6 system; the correspondences never go to memory.  The sums go through the fixed tree of the ICP above (thread, wave
+ * butterfly, waves in order, chunks in index order: the bits depend on the inputs only, no floating-point atomic), one header of
+ * 16 doubles and the count comes back per pass, and the host solves (one L D L^T without pivoting, a zero pivot gives a zero
+ * component), forms the estimate (Sophus's SE3::exp: translational part first, unit quaternion), composes it on the left and stops
+ * after the pass whose dx . dx < convergence_criterion^2.
+ * Not the reference's: the L D L^T's order (Eigen's pivots); the tree in place of TBB's deterministic reduce; the fixed rounding
+ * orders of the model; a non-finite row or one outside the int32 grid has no correspondence and the pass goes on.
+ * Refused before anything touches the GPU: NULL map or desc; a dtype other than F32 / F64; a row_stride below 3 (0 means 3); n > 0
+ * with NULL rows; more than 2^30 rows (UNSUPPORTED); a non-finite or negative max_distance, kernel_scale or convergence_criterion;
+ * unknown flags.  n == 0, an empty map or max_iterations <= 0: the identity, 0 iterations, no launch.
+ * On a map made with OUSTER_HIP_VOXEL_MAP_HOST every form runs host/registration_util.cpp on one core with left-fold sums (the
+ * _ref form) on rows in host memory and needs no context. */
+#define OUSTER_HIP_REG_SUMS 16   /* w, w s[3], j33, w sx sy, j44, w sx sz, w sy sz, j55, w r[3], w (s x r)[3]: SUMS of the model */
+typedef struct ouster_hip_registration_desc {
+    int32_t max_iterations;        /* in */
+    uint32_t flags;                /* in: 0 */
+    double convergence_criterion;  /* in */
+    double max_distance;           /* in: a correspondence is strictly nearer */
+    double kernel_scale;           /* in: k of the weight */
+    double pose[16];               /* out: row-major 4 x 4 */
+    uint32_t iterations;           /* out: passes run */
+    uint32_t converged;            /* out: the last pass met the criterion */
+    uint64_t correspondences;      /* out: of the last pass */
+} ouster_hip_registration_desc;
+/* rows[n][row_stride] in device memory */
+int ouster_hip_registration_align(const ouster_hip_voxel_map* map, const void* points, int32_t dtype, uint64_t n, uint64_t row_stride,
+                                  ouster_hip_registration_desc* desc);
+/* rows in host memory: pool memory in place, anything else through the context's scratch */
+int ouster_hip_registration_align_host(const ouster_hip_voxel_map* map, const void* points, int32_t dtype, uint64_t n,
+                                       uint64_t row_stride, ouster_hip_registration_desc* desc);
+/* One pass with everything a test compares.  A pose here is (qx, qy, qz, qw, tx, ty, tz). */
+typedef struct ouster_hip_registration_step_io {
+    const void* points;        /* in: [n][row_stride] of dtype */
+    uint64_t n, row_stride;
+    int32_t dtype;
+    int32_t has_estimate;      /* in: apply `estimate` to every row first (what a later pass does); 0: the rows as they are */
+    double estimate[7];
+    double max_distance, kernel_scale;
+    double* moved;             /* out [n][3]: the rows the pass associated */
+    uint8_t* flags;            /* out [n]: 1 where the row has a correspondence */
+    double* neighbours;        /* out [n][3]: what the map returned ((0, 0, 0): none) */
+    double* dist_sq;           /* out [n]: ... and its squared distance (max_distance^2: none) */
+    double sums[OUSTER_HIP_REG_SUMS];
+    uint64_t count;
+    double dx[6];
+    double next_estimate[7];   /* exp(dx) */
+} ouster_hip_registration_step_io;
+/* arrays in device memory; at least one row */
+int ouster_hip_registration_step(const ouster_hip_voxel_map* map, ouster_hip_registration_step_io* io);
+/* the same pass on a host map with arrays in host memory and left-fold sums */
+int ouster_hip_registration_step_ref(const ouster_hip_voxel_map* map, ouster_hip_registration_step_io* io);
+/* The reference's public build_linear_system on host arrays sources[n][3], targets[n][3]: left-fold sums; jtj36 row-major with the
+ * lower triangle filled and the upper left zero, as the reference leaves it. */
+int ouster_hip_build_linear_system_ref(const double* sources, const double* targets, uint64_t n, double kernel_scale, double* jtj36,
+                                       double* jtr6);
+/* AdaptiveThreshold's arithmetic (adaptive_threshold.cpp): |t| + 2 max_range sin(theta / 2) of a row-major 4 x 4 deviation, theta as
+ * Eigen's AngleAxisd(R).angle() gives it. */
+double ouster_hip_registration_model_error(const double* deviation16, double max_range);
+
 #ifdef __cplusplus
 }
 #endif

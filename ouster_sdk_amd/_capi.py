@@ -167,6 +167,21 @@ class VoxelMapInfo(C.Structure):   # ouster_hip_voxel_map_info
 
 VOXEL_MAP_HOST = 1   # OUSTER_HIP_VOXEL_MAP_HOST
 
+REG_SUMS = 16        # OUSTER_HIP_REG_SUMS
+
+
+class RegistrationDesc(C.Structure):   # ouster_hip_registration_desc
+    _fields_ = [("max_iterations", C.c_int32), ("flags", C.c_uint32), ("convergence_criterion", C.c_double),
+                ("max_distance", C.c_double), ("kernel_scale", C.c_double), ("pose", C.c_double * 16), ("iterations", C.c_uint32),
+                ("converged", C.c_uint32), ("correspondences", C.c_uint64)]
+
+
+class RegistrationStepIo(C.Structure):   # ouster_hip_registration_step_io
+    _fields_ = [("points", C.c_void_p), ("n", C.c_uint64), ("row_stride", C.c_uint64), ("dtype", C.c_int32),
+                ("has_estimate", C.c_int32), ("estimate", C.c_double * 7), ("max_distance", C.c_double), ("kernel_scale", C.c_double),
+                ("moved", C.c_void_p), ("flags", C.c_void_p), ("neighbours", C.c_void_p), ("dist_sq", C.c_void_p),
+                ("sums", C.c_double * REG_SUMS), ("count", C.c_uint64), ("dx", C.c_double * 6), ("next_estimate", C.c_double * 7)]
+
 
 class NormalsConsts(C.Structure):   # ouster_hip_normals_consts
     _fields_ = [("px_res_h", C.c_double), ("px_res_v", C.c_double), ("tan_safe", C.c_double), ("target_sq", C.c_double),
@@ -235,6 +250,9 @@ ABI_SYMBOLS = [
     "ouster_hip_voxel_map_remove_far", "ouster_hip_voxel_map_extract_far", "ouster_hip_voxel_map_extract_far_host",
     "ouster_hip_voxel_map_update", "ouster_hip_voxel_map_update_host", "ouster_hip_voxel_map_pointcloud",
     "ouster_hip_voxel_map_pointcloud_host", "ouster_hip_voxel_map_closest", "ouster_hip_voxel_map_closest_host",
+    # ICPRegistration: a cloud aligned to the resident voxel map
+    "ouster_hip_registration_align", "ouster_hip_registration_align_host", "ouster_hip_registration_step",
+    "ouster_hip_registration_step_ref", "ouster_hip_build_linear_system_ref", "ouster_hip_registration_model_error",
 ]
 
 _hip = None
@@ -422,6 +440,15 @@ def load_hip(private_path: Optional[str] = None):
             getattr(L, name).argtypes = [vp, vp, C.c_uint64, up]
         for name in ("ouster_hip_voxel_map_closest", "ouster_hip_voxel_map_closest_host"):
             getattr(L, name).argtypes = [vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_double, vp, vp]
+    if hasattr(L, "ouster_hip_registration_align"):
+        dp = C.POINTER(C.c_double)
+        for name in ("ouster_hip_registration_align", "ouster_hip_registration_align_host"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(RegistrationDesc)]
+        for name in ("ouster_hip_registration_step", "ouster_hip_registration_step_ref"):
+            getattr(L, name).argtypes = [vp, C.POINTER(RegistrationStepIo)]
+        L.ouster_hip_build_linear_system_ref.argtypes = [dp, dp, C.c_uint64, C.c_double, dp, dp]
+        L.ouster_hip_registration_model_error.argtypes = [dp, C.c_double]
+        L.ouster_hip_registration_model_error.restype = C.c_double
     if private_path is None:
         _hip = L
     return L

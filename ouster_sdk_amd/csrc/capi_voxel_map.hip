@@ -1,5 +1,6 @@
 // capi_voxel_map.hip -- the C ABI of the resident voxel map (k_voxel_map.hip, host/voxel_map_util.cpp): ouster_hip_voxel_map_*
 #include "capi_internal.h"
+#include "capi_voxel_map.h"
 #include "carve.h"
 #include "k_voxel_map.h"
 #include "voxel_map_host.h"
@@ -8,32 +9,9 @@
 
 using namespace ouster_hip_dev;
 
-struct ouster_hip_voxel_map {
-    ouster_hip_ctx* ctx = nullptr;
-    VoxelMapParams p;
-    HostVoxelMap* host = nullptr;   // OUSTER_HIP_VOXEL_MAP_HOST: everything below stays empty
-    VMapSet set[2];                 // the arrays in use and the set a removal compacts into
-    int cur = 0;
-    int32_t* table = nullptr;
-    uint32_t table_mask = 0;
-    uint64_t cap = 0;               // voxels each set holds
-    uint32_t n_vox = 0;
-    uint64_t n_pts = 0;
-    size_t bytes = 0;
-};
-
 namespace {
 
 constexpr uint64_t VMAP_MAX_SLOTS = 1ull << 32;   // cap * P stays below: positions in a cloud are 32-bit
-
-VMapDev dev_of(const ouster_hip_voxel_map* m) {
-    VMapDev d;
-    d.s = m->set[m->cur];
-    d.table = m->table, d.table_mask = m->table_mask;
-    d.n_vox = m->n_vox, d.cap = (uint32_t)m->cap, d.P = (uint32_t)m->p.max_points;
-    d.voxel_size = m->p.voxel_size, d.inv = m->p.inv, d.resolution_sq = m->p.resolution_sq;
-    return d;
-}
 
 void free_set(VMapSet& s) {
     counted_free(s.cell), counted_free(s.count), counted_free(s.pts);

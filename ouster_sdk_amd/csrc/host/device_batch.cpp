@@ -864,6 +864,13 @@ void DeviceFrameBatch::closest_in(const core::VoxelHashMap3d& map, double max_di
     map_nn_made_ = true;
 }
 
+core::Matrix4dR DeviceFrameBatch::align_voxels_to_map(const core::VoxelHashMap3d& map, const mapping::ICPRegistration& registration,
+                                                     double max_distance, double kernel_scale) {
+    ScopedContext on_my_context(ctx_);
+    voxel_map_handle_(map, "align_voxels_to_map");
+    return registration.align_device_points_to_map(static_cast<const double*>(d_vox_pts_.data()), vox_count_, 3, map, max_distance, kernel_scale);
+}
+
 double* DeviceFrameBatch::map_neighbors_device() { return map_nn_made_ ? static_cast<double*>(d_map_nn_.data()) : nullptr; }
 double* DeviceFrameBatch::map_neighbor_dist_device() { return map_nn_made_ ? static_cast<double*>(d_map_d2_.data()) : nullptr; }
 

@@ -31,6 +31,7 @@
 //                   an inactive source (fewer than 20 rows, or out of the loop already) returns at once.
 #include <hip/hip_runtime.h>
 
+#include "icp_sums_dev.h"
 #include "k_icp.h"
 #include "voxel_dev.h"
 
@@ -279,26 +280,6 @@ __global__ void __launch_bounds__(64) k_icp_median_many(IcpManyArgs m) {
 __device__ __forceinline__ double huber_weight(double r, double delta) {
     const double ar = fabs(r);
     return (ar <= delta || delta <= 0.0) ? 1.0 : delta / ar;
-}
-
-// acc[NS] of every thread of the workgroup -> partials[chunk][ofs .. ofs + NS): wave butterfly, then the waves in order
-template <int NS>
-__device__ __forceinline__ void block_sums(double (&acc)[NS], double* partial) {
-    __shared__ double lds[ICP_WG / 64][NS];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int s = 0; s < NS; ++s) acc[s] = acc[s] + __shfl_xor(acc[s], off, 64);
-    const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-    if (lane == 0)
-#pragma unroll
-        for (int s = 0; s < NS; ++s) lds[wave][s] = acc[s];
-    __syncthreads();
-    if (threadIdx.x < NS) {
-        double v = lds[0][threadIdx.x];
-        for (uint32_t w = 1; w < ICP_WG / 64; ++w) v = v + lds[w][threadIdx.x];
-        partial[threadIdx.x] = v;
-    }
 }
 
 // the rows a workgroup of the sum kernels folds: rows base + t + 256 k below n of one source, whose per-row outputs start at

@@ -20,6 +20,7 @@
 
 #include "k_voxel_map.h"
 #include "voxel_dev.h"
+#include "voxel_map_dev.h"
 
 #ifdef __HIPCC__
 #include <rocprim/device/device_radix_sort.hpp>
@@ -28,22 +29,6 @@
 
 namespace ouster_hip_dev {
 namespace {
-
-// the id of `k` in the map's table, VOXEL_NO_ID if it is not there
-__device__ __forceinline__ uint32_t vmap_lookup(const VMapDev& m, const VoxelKey& k) {
-    if (m.n_vox == 0) return VOXEL_NO_ID;
-    uint32_t s = voxel_hash(k) & m.table_mask;
-    for (uint32_t probe = 0; probe <= m.table_mask; ++probe) {
-        const int32_t id = m.table[s];
-        if (id == VOXEL_EMPTY) return VOXEL_NO_ID;
-        if ((uint32_t)id < m.n_vox) {
-            const VoxelKey o = m.s.cell[id];
-            if (o.x == k.x && o.y == k.y && o.z == k.z) return (uint32_t)id;
-        }
-        s = (s + 1) & m.table_mask;
-    }
-    return VOXEL_NO_ID;
-}
 
 // takes a free slot for `id`; false: every slot is held
 __device__ __forceinline__ bool vmap_insert(const VMapDev& m, const VoxelKey& k, uint32_t id) {
@@ -195,56 +180,14 @@ __global__ void __launch_bounds__(VOXEL_WG) k_vmap_cloud(VMapDev m, const uint32
     dst[0] = src[0], dst[1] = src[1], dst[2] = src[2];
 }
 
-// voxel_hash_map.cpp:158-166
-__constant__ int8_t VMAP_SHIFTS[27][3] = {
-    {0, 0, 0},   {1, 0, 0},   {-1, 0, 0},  {0, 1, 0},   {0, -1, 0},  {0, 0, 1},   {0, 0, -1},  {1, 1, 0},   {1, -1, 0},
-    {-1, 1, 0},  {-1, -1, 0}, {1, 0, 1},   {1, 0, -1},  {-1, 0, 1},  {-1, 0, -1}, {0, 1, 1},   {0, 1, -1},  {0, -1, 1},
-    {0, -1, -1}, {1, 1, 1},   {1, 1, -1},  {1, -1, 1},  {1, -1, -1}, {-1, 1, 1},  {-1, 1, -1}, {-1, -1, 1}, {-1, -1, -1}};
-
 template <class T>
 __global__ void __launch_bounds__(VOXEL_WG) k_vmap_closest(VMapDev m, VMapClosestArgs c) {
     const uint32_t i = blockIdx.x * VOXEL_WG + threadIdx.x;
     if (i >= c.q) return;
     const T* src = static_cast<const T*>(c.queries) + (uint64_t)i * c.stride;
     const double q[3] = {(double)src[0], (double)src[1], (double)src[2]};
-    double bx = 0.0, by = 0.0, bz = 0.0, best = c.max_distance_sq;
-    int32_t voxel[3];
-    const bool inside = axis_to_voxel(q[0], m.inv, voxel[0]) & axis_to_voxel(q[1], m.inv, voxel[1]) & axis_to_voxel(q[2], m.inv, voxel[2]);
-    if (inside && m.n_vox != 0) {
-        for (int sft = 0; sft < 27; ++sft) {
-            int64_t cell[3];
-            bool ok = true;
-            for (int d = 0; d < 3; ++d) {
-                cell[d] = (int64_t)voxel[d] + VMAP_SHIFTS[sft][d];
-                ok = ok && cell[d] >= -2147483648ll && cell[d] <= 2147483647ll;
-            }
-            if (!ok) continue;
-            double lb_sq = 0.0;
-            for (int d = 0; d < 3; ++d) {
-                const double lo = (double)cell[d] * m.voxel_size;
-                const double hi = lo + m.voxel_size;
-                if (q[d] < lo) {
-                    const double delta = lo - q[d];
-                    lb_sq = lb_sq + delta * delta;
-                } else if (q[d] > hi) {
-                    const double delta = q[d] - hi;
-                    lb_sq = lb_sq + delta * delta;
-                }
-            }
-            if (lb_sq >= best) continue;
-            const VoxelKey k{(int32_t)cell[0], (int32_t)cell[1], (int32_t)cell[2], 1};
-            const uint32_t id = vmap_lookup(m, k);
-            if (id == VOXEL_NO_ID) continue;
-            const uint32_t cnt = m.s.count[id] <= m.P ? m.s.count[id] : m.P;
-            const double* held = m.s.pts + (uint64_t)id * m.P * 3;
-            for (uint32_t h = 0; h < cnt; ++h) {
-                const double x = held[3 * h], y = held[3 * h + 1], z = held[3 * h + 2];
-                const double dx = x - q[0], dy = y - q[1], dz = z - q[2];
-                const double d2 = (dx * dx + dy * dy) + dz * dz;
-                if (d2 < best) best = d2, bx = x, by = y, bz = z;
-            }
-        }
-    }
+    double bx, by, bz, best;
+    vmap_closest_point(m, q, c.max_distance_sq, bx, by, bz, best);
     double* dst = c.out_points + 3 * (uint64_t)i;
     dst[0] = bx, dst[1] = by, dst[2] = bz;
     c.out_dist_sq[i] = best;

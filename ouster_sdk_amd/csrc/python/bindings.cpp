@@ -22,6 +22,8 @@
 #include "ouster/core/image_processing.h"
 #include "ouster/core/lidar_scan.h"
 #include "ouster/core/voxel_hash_map.h"
+#include "ouster/mapping/adaptive_threshold.h"
+#include "ouster/mapping/icp_registration.h"
 #include "ouster/hip/frame_stream.h"
 #include "ouster/osf/osf.h"
 #include "ouster/pcap/indexed_pcap_reader.h"
@@ -1006,6 +1008,62 @@ PYBIND11_MODULE(core, m) {
             .def_property_readonly("num_points", &Map::num_points)
             .def_property_readonly("device_bytes", &Map::device_bytes)
             .def_property_readonly("device", &Map::device);
+    }
+
+    // ICPRegistration, AdaptiveThreshold, build_linear_system: the names, keywords and defaults of ouster.sdk.mapping; refusals as
+    // ValueError
+    {
+        namespace om = ouster::sdk::mapping;
+        namespace oc = ouster::sdk::core;
+        using darr = py::array_t<double, py::array::c_style | py::array::forcecast>;
+        auto to_numpy4 = [](const oc::mat4d& a) {
+            py::array_t<double> out({py::ssize_t(4), py::ssize_t(4)});
+            std::memcpy(out.mutable_data(), a.data(), 16 * sizeof(double));
+            return out;
+        };
+        py::class_<om::ICPRegistration>(m, "ICPRegistration")
+            .def(py::init<int, double, int>(), py::arg("max_num_iterations") = 50, py::arg("convergence_criterion") = 0.0001,
+                 py::arg("max_num_threads") = 0)
+            .def_readwrite("max_num_iterations", &om::ICPRegistration::max_num_iterations_)
+            .def_readwrite("convergence_criterion", &om::ICPRegistration::convergence_criterion_)
+            .def_readwrite("max_num_threads", &om::ICPRegistration::max_num_threads_)
+            .def(
+                "align_points_to_map",
+                [to_numpy4](const om::ICPRegistration& self, const darr& frame, const oc::VoxelHashMap3d& voxel_map, double max_distance,
+                            double kernel_scale) {
+                    if (frame.ndim() != 2 || frame.shape(1) != 3) throw std::invalid_argument("align_points_to_map expects an Nx3 array");
+                    return to_numpy4(self.align_array_to_map(frame.data(), static_cast<size_t>(frame.shape(0)), voxel_map, max_distance, kernel_scale));
+                },
+                py::arg("frame"), py::arg("voxel_map"), py::arg("max_distance"), py::arg("kernel_scale"));
+        py::class_<om::AdaptiveThreshold>(m, "AdaptiveThreshold")
+            .def(py::init<double, double, double>(), py::arg("max_range"), py::arg("initial_threshold") = 2.0,
+                 py::arg("min_motion_threshold") = 0.01)
+            .def_readwrite("max_range", &om::AdaptiveThreshold::max_range_)
+            .def_readwrite("min_motion_threshold", &om::AdaptiveThreshold::min_motion_threshold_)
+            .def(
+                "update_model_deviation",
+                [](om::AdaptiveThreshold& self, const darr& deviation) {
+                    if (deviation.ndim() != 2 || deviation.shape(0) != 4 || deviation.shape(1) != 4)
+                        throw std::invalid_argument("update_model_deviation expects a 4x4 array");
+                    self.update_model_deviation(oc::mat4d::FromRowMajor(deviation.data()));
+                },
+                py::arg("current_deviation"))
+            .def("compute_threshold", &om::AdaptiveThreshold::compute_threshold);
+        m.def(
+            "build_linear_system",
+            [](const darr& sources, const darr& targets, double kernel_scale) {
+                if (sources.ndim() != 2 || sources.shape(1) != 3 || targets.ndim() != 2 || targets.shape(1) != 3 || sources.shape(0) != targets.shape(0))
+                    throw std::invalid_argument("build_linear_system expects two Nx3 arrays of equal length");
+                om::Correspondences c(static_cast<size_t>(sources.shape(0)));
+                for (size_t i = 0; i < c.size(); ++i)
+                    for (int k = 0; k < 3; ++k) c[i].first[k] = sources.data()[3 * i + k], c[i].second[k] = targets.data()[3 * i + k];
+                const om::LinearSystem ls = om::build_linear_system(c, kernel_scale);
+                py::array_t<double> jtj({py::ssize_t(6), py::ssize_t(6)}), jtr(py::ssize_t(6));
+                std::memcpy(jtj.mutable_data(), ls.first.data(), 36 * sizeof(double));
+                std::memcpy(jtr.mutable_data(), ls.second.data(), 6 * sizeof(double));
+                return py::make_tuple(jtj, jtr);
+            },
+            py::arg("sources"), py::arg("targets"), py::arg("kernel_scale"));
     }
 
     // ICP: the names, keywords and defaults of ouster.sdk.algorithm.point_to_point_align / point_to_plane_align; the reference's
