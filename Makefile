@@ -96,11 +96,7 @@ oracle:
 
 cpptests: $(LIB)/libouster_core_amd.so
 	$(MAKE) -C tests/cpp -s
-	$(MAKE) -C tests/cpp -s tonemap_ref_sanitized   # runs it: the host half under ASan / UBSan
-	$(MAKE) -C tests/cpp -f icp_target.mk -s        # the programs of the IcpTarget tests, a makefile of their own
-	$(MAKE) -C tests/cpp -f voxel_map.mk -s         # the programs of the voxel map tests, likewise
-	$(MAKE) -C tests/cpp -f registration.mk -s      # the programs of the registration tests, likewise
-	$(MAKE) -C tests/cpp -f registration.mk -s registration_ref_sanitized   # runs it: the host half under ASan / UBSan
+	$(MAKE) -C tests/cpp -s sanitized   # runs them: the host halves and the header units under ASan / UBSan, programs of their own
 	$(MAKE) -C oracle -s refcpptests
 
 clean:

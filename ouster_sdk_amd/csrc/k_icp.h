@@ -118,12 +118,15 @@ hipError_t launch_icp_correspond(const IcpArgs& a, hipStream_t st);   // nn, r, 
 hipError_t launch_icp_rows_used(const IcpArgs& a, hipStream_t st);    // pass.count: the rows that take part (after the grid)
 hipError_t launch_icp_correspond_many(const IcpManyArgs& m, hipStream_t st);   // the same of every active source, a workgroup per chunk
 
-// The device-wide pieces (hipcc only): the bytes of temporary storage a call needs, the grid once per call and one pass, both on the
-// stream without a synchronisation.  `va` carries the target-side arrays for the launchers of k_voxel.h (n = n_tgt).
+// The device-wide pieces: the bytes of temporary storage a call needs, the grid once per call and one pass, both on the stream
+// without a synchronisation.  `va` carries the target-side arrays for voxel_group_run of k_voxel.h (n = n_tgt); the grid needs
+// voxel_temp_bytes(n_tgt) of temp and is compiled wherever the grouping is, the rest by hipcc only.
 // ev: nullptr, or events recorded after the grid (1) / after correspond, median and sums (3).
+#if OUSTER_DEVICE_WIDE
+hipError_t icp_grid_run(const IcpArgs& a, const VoxelArgs& va, void* temp, size_t temp_bytes, hipStream_t st);
+#endif
 #ifdef __HIPCC__
 hipError_t icp_temp_bytes(uint32_t n_src, uint32_t n_tgt, size_t* bytes);
-hipError_t icp_grid_run(const IcpArgs& a, const VoxelArgs& va, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t icp_pass_run(const IcpArgs& a, void* temp, size_t temp_bytes, hipStream_t st, hipEvent_t* ev = nullptr);
 // The many-source pass: correspond, a segmented sum of the flags and a segmented radix sort of the keys over the sources' rows,
 // the medians, the sum kernels and a fold per source; the active sources' headers are complete when the stream gets there.

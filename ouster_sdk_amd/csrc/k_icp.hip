@@ -5,8 +5,8 @@
 // The target grid, once per call (cell = max_corr_dist):
 // k_icp_keys        one thread per target row: does it take part (finite point; with normals a finite normal longer than 1e-12),
 //                   its int32 cell, the status word where no int32 holds it.
-// (k_voxel.hip)     k_voxel_insert, k_voxel_first, scan, k_voxel_ids, stable radix sort by cell id, k_voxel_segments: a cell's rows
-//                   contiguous and in ascending index.
+// (k_voxel.hip)     voxel_group_run -- k_voxel_insert, k_voxel_first, scan, k_voxel_ids, stable radix sort by cell id,
+//                   k_voxel_segments: a cell's rows contiguous and in ascending index.
 // k_icp_slots       one thread per table slot: the cell and the range of its rows, so that a probe reads one 16-byte slot.
 // k_icp_gather      the participating points (and unit normals) widened and copied in sorted order; sidx keeps the original index.
 // A pass:
@@ -38,7 +38,6 @@
 #ifdef __HIPCC__
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_reduce.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 #include <rocprim/device/device_segmented_reduce.hpp>
 #endif
@@ -463,6 +462,18 @@ hipError_t launch_icp_correspond_many(const IcpManyArgs& m, hipStream_t st) {
     return hipGetLastError();
 }
 
+#if OUSTER_DEVICE_WIDE
+hipError_t icp_grid_run(const IcpArgs& a, const VoxelArgs& va, void* temp, size_t temp_bytes, hipStream_t st) {
+    if (a.n_tgt == 0 || va.n != a.n_tgt) return hipErrorInvalidValue;
+    // every call starts from a clean header (and, in voxel_group_run, an empty table)
+    RUN_TRY(hipMemsetAsync(a.rb, 0, sizeof(IcpReadback), st));
+    RUN_TRY(launch_icp_keys(a, st));
+    RUN_TRY(voxel_group_run(va, temp, temp_bytes, st));
+    RUN_TRY(launch_icp_slots(a, st));
+    return launch_icp_gather(a, st);
+}
+#endif
+
 #ifdef __HIPCC__
 hipError_t icp_temp_bytes(uint32_t n_src, uint32_t n_tgt, size_t* bytes) {
     size_t grid = 0, sort = 0, reduce = 0;
@@ -479,64 +490,40 @@ hipError_t icp_temp_bytes(uint32_t n_src, uint32_t n_tgt, size_t* bytes) {
     return hipSuccess;
 }
 
-#define ICP_TRY(expr)                      \
-    do {                                   \
-        const hipError_t e_ = (expr);      \
-        if (e_ != hipSuccess) return e_;   \
-    } while (0)
-
-hipError_t icp_grid_run(const IcpArgs& a, const VoxelArgs& va, void* temp, size_t temp_bytes, hipStream_t st) {
-    if (a.n_tgt == 0 || va.n != a.n_tgt) return hipErrorInvalidValue;
-    // every call starts from an empty table and a clean header
-    ICP_TRY(hipMemsetAsync(a.table, 0xff, ((size_t)a.table_mask + 1) * sizeof(int32_t), st));
-    ICP_TRY(hipMemsetAsync(a.rb, 0, sizeof(IcpReadback), st));
-    ICP_TRY(launch_icp_keys(a, st));
-    ICP_TRY(launch_voxel_insert(va, st));
-    ICP_TRY(launch_voxel_first(va, st));
-    size_t bytes = temp_bytes;
-    ICP_TRY(rocprim::exclusive_scan(temp, bytes, va.first, va.first_id, 0u, (size_t)va.n, rocprim::plus<uint32_t>(), st));
-    ICP_TRY(launch_voxel_ids(va, st));
-    bytes = temp_bytes;
-    ICP_TRY(rocprim::radix_sort_pairs(temp, bytes, va.vid, va.svid, va.idx, va.sidx, (size_t)va.n, 0, voxel_sort_bits(va.n), st));
-    ICP_TRY(launch_voxel_segments(va, st));
-    ICP_TRY(launch_icp_slots(a, st));
-    return launch_icp_gather(a, st);
-}
-
 hipError_t icp_many_temp_bytes(uint32_t n_rows, uint32_t n_sources, size_t* bytes) {
     size_t sort = 0, reduce = 0;
     uint64_t* k = nullptr;
     uint32_t* u = nullptr;
-    ICP_TRY(rocprim::segmented_radix_sort_keys(nullptr, sort, k, k, n_rows, n_sources, u, u, 0, 64));
-    ICP_TRY(rocprim::segmented_reduce(nullptr, reduce, u, u, n_sources, u, u, rocprim::plus<uint32_t>(), 0u));
+    RUN_TRY(rocprim::segmented_radix_sort_keys(nullptr, sort, k, k, n_rows, n_sources, u, u, 0, 64));
+    RUN_TRY(rocprim::segmented_reduce(nullptr, reduce, u, u, n_sources, u, u, rocprim::plus<uint32_t>(), 0u));
     *bytes = sort > reduce ? sort : reduce;
     return hipSuccess;
 }
 
 hipError_t icp_many_pass_run(const IcpManyArgs& m, void* temp, size_t temp_bytes, hipStream_t st) {
     if (m.n_sources == 0 || m.n_chunks == 0 || m.n_rows == 0) return hipErrorInvalidValue;
-    ICP_TRY(launch_icp_correspond_many(m, st));
+    RUN_TRY(launch_icp_correspond_many(m, st));
     // an inactive source's segment is empty (seg_end == seg_begin): nothing of it is reduced or sorted
     size_t bytes = temp_bytes;
-    ICP_TRY(rocprim::segmented_reduce(temp, bytes, m.q.flag, m.counts, m.n_sources, m.seg_begin, m.seg_end, rocprim::plus<uint32_t>(), 0u, st));
+    RUN_TRY(rocprim::segmented_reduce(temp, bytes, m.q.flag, m.counts, m.n_sources, m.seg_begin, m.seg_end, rocprim::plus<uint32_t>(), 0u, st));
     bytes = temp_bytes;
-    ICP_TRY(rocprim::segmented_radix_sort_keys(temp, bytes, m.q.key, m.key_sorted, m.n_rows, m.n_sources, m.seg_begin, m.seg_end, 0, 64, st));
+    RUN_TRY(rocprim::segmented_radix_sort_keys(temp, bytes, m.q.key, m.key_sorted, m.n_rows, m.n_sources, m.seg_begin, m.seg_end, 0, 64, st));
     hipLaunchKernelGGL(k_icp_median_many, dim3((m.n_sources + 63) / 64), dim3(64), 0, st, m);
-    ICP_TRY(hipGetLastError());
+    RUN_TRY(hipGetLastError());
     if (m.q.plane) {
         hipLaunchKernelGGL(k_icp_sums_plane_many, dim3(m.n_chunks), dim3(ICP_WG), 0, st, m);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_icp_fold_many, dim3(m.n_sources), dim3(64), 0, st, m, 0u, 27u, 0);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
     } else {
         hipLaunchKernelGGL(k_icp_sums_point_a_many, dim3(m.n_chunks), dim3(ICP_WG), 0, st, m);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_icp_fold_many, dim3(m.n_sources), dim3(64), 0, st, m, 0u, 7u, 1);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_icp_sums_point_b_many, dim3(m.n_chunks), dim3(ICP_WG), 0, st, m);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_icp_fold_many, dim3(m.n_sources), dim3(64), 0, st, m, 7u, 9u, 0);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
     }
     return hipSuccess;
 }
@@ -544,31 +531,31 @@ hipError_t icp_many_pass_run(const IcpManyArgs& m, void* temp, size_t temp_bytes
 hipError_t icp_pass_run(const IcpArgs& a, void* temp, size_t temp_bytes, hipStream_t st, hipEvent_t* ev) {
     if (a.n_src == 0) return hipErrorInvalidValue;
     const uint32_t chunks = icp_chunks(a.n_src);
-    ICP_TRY(launch_icp_correspond(a, st));
-    if (ev) ICP_TRY(hipEventRecord(ev[0], st));
+    RUN_TRY(launch_icp_correspond(a, st));
+    if (ev) RUN_TRY(hipEventRecord(ev[0], st));
     size_t bytes = temp_bytes;
-    ICP_TRY(rocprim::reduce(temp, bytes, a.flag, &a.rb->pass.count, 0u, (size_t)a.n_src, rocprim::plus<uint32_t>(), st));
+    RUN_TRY(rocprim::reduce(temp, bytes, a.flag, &a.rb->pass.count, 0u, (size_t)a.n_src, rocprim::plus<uint32_t>(), st));
     bytes = temp_bytes;
-    ICP_TRY(rocprim::radix_sort_keys(temp, bytes, a.key, a.key_sorted, (size_t)a.n_src, 0, 64, st));
+    RUN_TRY(rocprim::radix_sort_keys(temp, bytes, a.key, a.key_sorted, (size_t)a.n_src, 0, 64, st));
     hipLaunchKernelGGL(k_icp_median, dim3(1), dim3(64), 0, st, a);
-    ICP_TRY(hipGetLastError());
-    if (ev) ICP_TRY(hipEventRecord(ev[1], st));
+    RUN_TRY(hipGetLastError());
+    if (ev) RUN_TRY(hipEventRecord(ev[1], st));
     if (a.plane) {
         hipLaunchKernelGGL(k_icp_sums_plane, dim3(chunks), dim3(ICP_WG), 0, st, a);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_icp_fold, dim3(1), dim3(64), 0, st, a, 0u, 27u, chunks, 0);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
     } else {
         hipLaunchKernelGGL(k_icp_sums_point_a, dim3(chunks), dim3(ICP_WG), 0, st, a);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_icp_fold, dim3(1), dim3(64), 0, st, a, 0u, 7u, chunks, 1);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_icp_sums_point_b, dim3(chunks), dim3(ICP_WG), 0, st, a);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_icp_fold, dim3(1), dim3(64), 0, st, a, 7u, 9u, chunks, 0);
-        ICP_TRY(hipGetLastError());
+        RUN_TRY(hipGetLastError());
     }
-    if (ev) ICP_TRY(hipEventRecord(ev[2], st));
+    if (ev) RUN_TRY(hipEventRecord(ev[2], st));
     return hipSuccess;
 }
 #endif

@@ -74,13 +74,35 @@ inline uint32_t voxel_sort_bits(uint32_t n) {
     return bits;
 }
 
-// The device-wide pieces taken from rocPRIM (compiled with hipcc only): the bytes of temporary storage the scan and the sort of n
-// elements need, and the whole pipeline on the stream -- table reset, the kernels above, scan, stable radix sort, scan --
-// without a synchronisation.  temp: at least voxel_temp_bytes(n), 256-byte aligned.  ev: nullptr, or OUSTER_HIP_VOXEL_PHASES + 1
-// events: ev[0] is recorded before the first step and ev[k + 1] after phase k (reset + keys, insert, first + scan + ids, sort,
-// segments, gather + reduce + scan, write).
-#ifdef __HIPCC__
+// The run functions of k_voxel.hip, k_icp.hip's grid and k_voxel_map.hip call rocPRIM's scan and radix sort: they are compiled by
+// hipcc, and by the host-lanes build of tests/cpp, whose hip/hip_runtime.h announces itself and stands in for those two calls.
+#if defined(__HIPCC__) || defined(OUSTER_HOST_LANES)
+#define OUSTER_DEVICE_WIDE 1
+#else
+#define OUSTER_DEVICE_WIDE 0
+#endif
+
+// every step of a run function: the first error ends the run
+#define RUN_TRY(expr)                      \
+    do {                                   \
+        const hipError_t e_ = (expr);      \
+        if (e_ != hipSuccess) return e_;   \
+    } while (0)
+
+#if OUSTER_DEVICE_WIDE
+// the bytes of temporary storage the scan and the sort of a grouping of n rows need
 hipError_t voxel_temp_bytes(uint32_t n, size_t* bytes);
+// Groups the rows by voxel, on the stream and without a synchronisation: table reset, insert, first, exclusive scan of the first
+// flags, ids, stable radix sort of the row indices over voxel_sort_bits(n) bits, segments.  a.keys are written already (and
+// a.hdr reset) by what runs before on the stream; fills slot .. seg_end and a.hdr->n_vox.  The one place this sequence is written:
+// the row order of every result of voxel_run, icp_grid_run and vmap_add_prepare depends on it.
+// temp: at least voxel_temp_bytes(n), 256-byte aligned.  ev: nullptr, or 5 events, recorded after the table reset (which so stays in
+// the caller's phase of resets and keys, as include/ouster_hip.h names it), after the insert, after the ids, after the sort and
+// after the segments.
+hipError_t voxel_group_run(const VoxelArgs& a, void* temp, size_t temp_bytes, hipStream_t st, hipEvent_t* ev = nullptr);
+// The whole down-sampling: header reset, keys, the grouping, then gather + reduce + scan (AVERAGE, NORMALS) and the write.
+// ev: nullptr, or OUSTER_HIP_VOXEL_PHASES + 1 events: ev[0] is recorded before the first step and ev[k + 1] after phase k (reset +
+// keys, insert, first + scan + ids, sort, segments, gather + reduce + scan, write).
 hipError_t voxel_run(const VoxelArgs& a, void* temp, size_t temp_bytes, hipStream_t st, hipEvent_t* ev = nullptr);
 #endif
 

@@ -20,7 +20,7 @@
 #include "k_voxel.h"
 #include "voxel_dev.h"
 
-#ifdef __HIPCC__
+#if OUSTER_DEVICE_WIDE
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #endif
@@ -258,7 +258,7 @@ hipError_t launch_voxel_write(const VoxelArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-#ifdef __HIPCC__
+#if OUSTER_DEVICE_WIDE
 hipError_t voxel_temp_bytes(uint32_t n, size_t* bytes) {
     size_t scan = 0, sort = 0;
     uint32_t* u = nullptr;
@@ -270,44 +270,45 @@ hipError_t voxel_temp_bytes(uint32_t n, size_t* bytes) {
     return hipSuccess;
 }
 
-#define VOXEL_TRY(expr)                    \
-    do {                                   \
-        const hipError_t e_ = (expr);      \
-        if (e_ != hipSuccess) return e_;   \
-    } while (0)
+hipError_t voxel_group_run(const VoxelArgs& a, void* temp, size_t temp_bytes, hipStream_t st, hipEvent_t* ev) {
+    if (a.n == 0) return hipSuccess;
+    int phase = 0;
+    auto mark = [&]() -> hipError_t { return ev ? hipEventRecord(ev[phase++], st) : hipSuccess; };
+    // a stale table is the obvious bug of a reused workspace: every call starts from an empty one
+    RUN_TRY(hipMemsetAsync(a.table, 0xff, ((size_t)a.table_mask + 1) * sizeof(int32_t), st));
+    RUN_TRY(mark());
+    RUN_TRY(launch_voxel_insert(a, st));
+    RUN_TRY(mark());
+    RUN_TRY(launch_voxel_first(a, st));
+    size_t bytes = temp_bytes;
+    RUN_TRY(rocprim::exclusive_scan(temp, bytes, a.first, a.first_id, 0u, (size_t)a.n, rocprim::plus<uint32_t>(), st));
+    RUN_TRY(launch_voxel_ids(a, st));
+    RUN_TRY(mark());
+    bytes = temp_bytes;
+    RUN_TRY(rocprim::radix_sort_pairs(temp, bytes, a.vid, a.svid, a.idx, a.sidx, (size_t)a.n, 0, voxel_sort_bits(a.n), st));
+    RUN_TRY(mark());
+    RUN_TRY(launch_voxel_segments(a, st));
+    return mark();
+}
 
 hipError_t voxel_run(const VoxelArgs& a, void* temp, size_t temp_bytes, hipStream_t st, hipEvent_t* ev) {
     if (a.n == 0) return hipSuccess;
     const bool folds = a.form == VOXEL_FORM_AVERAGE || a.form == VOXEL_FORM_NORMALS;
-    int phase = 0;
-    auto mark = [&]() -> hipError_t { return ev ? hipEventRecord(ev[phase++], st) : hipSuccess; };
-    VOXEL_TRY(mark());
-    // a stale table is the obvious bug of a reused workspace: every call starts from an empty one
-    VOXEL_TRY(hipMemsetAsync(a.table, 0xff, ((size_t)a.table_mask + 1) * sizeof(int32_t), st));
-    VOXEL_TRY(hipMemsetAsync(a.hdr, 0, sizeof(VoxelHeader), st));
-    VOXEL_TRY(launch_voxel_keys(a, st));
-    VOXEL_TRY(mark());
-    VOXEL_TRY(launch_voxel_insert(a, st));
-    VOXEL_TRY(mark());
-    VOXEL_TRY(launch_voxel_first(a, st));
-    size_t bytes = temp_bytes;
-    VOXEL_TRY(rocprim::exclusive_scan(temp, bytes, a.first, a.first_id, 0u, (size_t)a.n, rocprim::plus<uint32_t>(), st));
-    VOXEL_TRY(launch_voxel_ids(a, st));
-    VOXEL_TRY(mark());
-    bytes = temp_bytes;
-    VOXEL_TRY(rocprim::radix_sort_pairs(temp, bytes, a.vid, a.svid, a.idx, a.sidx, (size_t)a.n, 0, voxel_sort_bits(a.n), st));
-    VOXEL_TRY(mark());
-    VOXEL_TRY(launch_voxel_segments(a, st));
-    VOXEL_TRY(mark());
+    // ev[0] before the first step; ev[1] .. ev[5] are the grouping's, whose first closes the phase of the resets and the keys;
+    // ev[6], ev[7] after the fold and the write
+    if (ev) RUN_TRY(hipEventRecord(ev[0], st));
+    RUN_TRY(hipMemsetAsync(a.hdr, 0, sizeof(VoxelHeader), st));
+    RUN_TRY(launch_voxel_keys(a, st));
+    RUN_TRY(voxel_group_run(a, temp, temp_bytes, st, ev ? ev + 1 : nullptr));
     if (folds) {
-        VOXEL_TRY(launch_voxel_gather(a, st));
-        VOXEL_TRY(launch_voxel_reduce(a, st));
-        bytes = temp_bytes;
-        VOXEL_TRY(rocprim::exclusive_scan(temp, bytes, a.keep, a.pos, 0u, (size_t)a.n, rocprim::plus<uint32_t>(), st));
+        RUN_TRY(launch_voxel_gather(a, st));
+        RUN_TRY(launch_voxel_reduce(a, st));
+        size_t bytes = temp_bytes;
+        RUN_TRY(rocprim::exclusive_scan(temp, bytes, a.keep, a.pos, 0u, (size_t)a.n, rocprim::plus<uint32_t>(), st));
     }
-    VOXEL_TRY(mark());
-    VOXEL_TRY(launch_voxel_write(a, st));
-    return mark();
+    if (ev) RUN_TRY(hipEventRecord(ev[6], st));
+    RUN_TRY(launch_voxel_write(a, st));
+    return ev ? hipEventRecord(ev[7], st) : hipSuccess;
 }
 #endif
 

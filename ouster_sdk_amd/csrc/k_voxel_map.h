@@ -69,10 +69,10 @@ struct VMapClosestArgs {
     double* out_dist_sq;    // [q]
 };
 
-#ifdef __HIPCC__
+#if OUSTER_DEVICE_WIDE
 // bytes of rocPRIM temporary storage for scans of n elements (the call-local grid's own needs are voxel_temp_bytes)
 hipError_t vmap_temp_bytes(uint32_t n, size_t* bytes);
-// the call-local grid (k_voxel.hip's launchers, unchanged), k_vmap_find, the scan of the new flags, hdr->n_new.  Publishes nothing.
+// the header resets, the call-local grid (k_voxel.hip's keys and voxel_group_run), k_vmap_find, the scan of the new flags, hdr->n_new.  Publishes nothing.
 hipError_t vmap_add_prepare(const VoxelArgs& a, const VMapDev& m, const VMapAddArgs& x, void* temp, size_t temp_bytes, hipStream_t st);
 // k_vmap_publish, k_vmap_admit: m has room for n_vox + n_new voxels
 hipError_t vmap_add_commit(const VoxelArgs& a, const VMapDev& m, const VMapAddArgs& x, hipStream_t st);

@@ -2,8 +2,8 @@
 // with -ffp-contract=off: every multiply, add and subtract below is one IEEE double operation in the model's order.  No
 // floating-point atomic anywhere; a voxel's points are only ever written by the one thread that owns the voxel in that launch.
 //
-// add_points   the batch alone goes through k_voxel.hip's own steps (keys, insert, first, scan, ids, stable sort, segments): call-
-//              local voxels in first-seen order with contiguous, input-ordered segments.
+// add_points   the batch alone goes through k_voxel.hip's own steps (keys, then voxel_group_run: insert, first, scan, ids, stable
+//              sort, segments): call-local voxels in first-seen order with contiguous, input-ordered segments.
 //   k_vmap_find     one thread per call-local voxel probes the map's table: an id already in use, or "new".
 //   (exclusive scan of the "new" flags: new voxels are numbered in first-seen order after the ids in use; the host reads the count
 //   and grows the arrays before anything is published)
@@ -22,8 +22,7 @@
 #include "voxel_dev.h"
 #include "voxel_map_dev.h"
 
-#ifdef __HIPCC__
-#include <rocprim/device/device_radix_sort.hpp>
+#if OUSTER_DEVICE_WIDE
 #include <rocprim/device/device_scan.hpp>
 #endif
 
@@ -197,13 +196,7 @@ inline dim3 vmap_grid(uint64_t n) { return dim3((uint32_t)((n + VOXEL_WG - 1) / 
 
 }  // namespace
 
-#ifdef __HIPCC__
-#define VMAP_TRY(expr)                     \
-    do {                                   \
-        const hipError_t e_ = (expr);      \
-        if (e_ != hipSuccess) return e_;   \
-    } while (0)
-
+#if OUSTER_DEVICE_WIDE
 hipError_t vmap_temp_bytes(uint32_t n, size_t* bytes) {
     uint32_t* u = nullptr;
     *bytes = 0;
@@ -212,22 +205,14 @@ hipError_t vmap_temp_bytes(uint32_t n, size_t* bytes) {
 
 hipError_t vmap_add_prepare(const VoxelArgs& a, const VMapDev& m, const VMapAddArgs& x, void* temp, size_t temp_bytes, hipStream_t st) {
     if (a.n == 0) return hipSuccess;
-    VMAP_TRY(hipMemsetAsync(a.table, 0xff, ((size_t)a.table_mask + 1) * sizeof(int32_t), st));
-    VMAP_TRY(hipMemsetAsync(a.hdr, 0, sizeof(VoxelHeader), st));
-    VMAP_TRY(hipMemsetAsync(x.hdr, 0, sizeof(VMapHeader), st));
-    VMAP_TRY(launch_voxel_keys(a, st));
-    VMAP_TRY(launch_voxel_insert(a, st));
-    VMAP_TRY(launch_voxel_first(a, st));
-    size_t bytes = temp_bytes;
-    VMAP_TRY(rocprim::exclusive_scan(temp, bytes, a.first, a.first_id, 0u, (size_t)a.n, rocprim::plus<uint32_t>(), st));
-    VMAP_TRY(launch_voxel_ids(a, st));
-    bytes = temp_bytes;
-    VMAP_TRY(rocprim::radix_sort_pairs(temp, bytes, a.vid, a.svid, a.idx, a.sidx, (size_t)a.n, 0, voxel_sort_bits(a.n), st));
-    VMAP_TRY(launch_voxel_segments(a, st));
+    RUN_TRY(hipMemsetAsync(a.hdr, 0, sizeof(VoxelHeader), st));
+    RUN_TRY(hipMemsetAsync(x.hdr, 0, sizeof(VMapHeader), st));
+    RUN_TRY(launch_voxel_keys(a, st));
+    RUN_TRY(voxel_group_run(a, temp, temp_bytes, st));
     hipLaunchKernelGGL(k_vmap_find, vmap_grid(a.n), dim3(VOXEL_WG), 0, st, a, m, x);
-    VMAP_TRY(hipGetLastError());
-    bytes = temp_bytes;
-    VMAP_TRY(rocprim::exclusive_scan(temp, bytes, x.is_new, x.new_pos, 0u, (size_t)a.n, rocprim::plus<uint32_t>(), st));
+    RUN_TRY(hipGetLastError());
+    size_t bytes = temp_bytes;
+    RUN_TRY(rocprim::exclusive_scan(temp, bytes, x.is_new, x.new_pos, 0u, (size_t)a.n, rocprim::plus<uint32_t>(), st));
     hipLaunchKernelGGL(k_vmap_add_header, dim3(1), dim3(1), 0, st, a, x);
     return hipGetLastError();
 }
@@ -235,7 +220,7 @@ hipError_t vmap_add_prepare(const VoxelArgs& a, const VMapDev& m, const VMapAddA
 hipError_t vmap_add_commit(const VoxelArgs& a, const VMapDev& m, const VMapAddArgs& x, hipStream_t st) {
     if (a.n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_vmap_publish, vmap_grid(a.n), dim3(VOXEL_WG), 0, st, a, m, x);
-    VMAP_TRY(hipGetLastError());
+    RUN_TRY(hipGetLastError());
     if (a.f32) hipLaunchKernelGGL(k_vmap_admit<float>, vmap_grid(a.n), dim3(VOXEL_WG), 0, st, a, m, x);
     else hipLaunchKernelGGL(k_vmap_admit<double>, vmap_grid(a.n), dim3(VOXEL_WG), 0, st, a, m, x);
     return hipGetLastError();
@@ -243,13 +228,13 @@ hipError_t vmap_add_commit(const VoxelArgs& a, const VMapDev& m, const VMapAddAr
 
 hipError_t vmap_far_prepare(const VMapDev& m, const VMapFarArgs& f, void* temp, size_t temp_bytes, hipStream_t st) {
     if (m.n_vox == 0) return hipSuccess;
-    VMAP_TRY(hipMemsetAsync(f.hdr, 0, sizeof(VMapHeader), st));
+    RUN_TRY(hipMemsetAsync(f.hdr, 0, sizeof(VMapHeader), st));
     hipLaunchKernelGGL(k_vmap_far, vmap_grid(m.n_vox), dim3(VOXEL_WG), 0, st, m, f);
-    VMAP_TRY(hipGetLastError());
+    RUN_TRY(hipGetLastError());
     size_t bytes = temp_bytes;
-    VMAP_TRY(rocprim::exclusive_scan(temp, bytes, f.keep, f.keep_pos, 0u, (size_t)m.n_vox, rocprim::plus<uint32_t>(), st));
+    RUN_TRY(rocprim::exclusive_scan(temp, bytes, f.keep, f.keep_pos, 0u, (size_t)m.n_vox, rocprim::plus<uint32_t>(), st));
     bytes = temp_bytes;
-    VMAP_TRY(rocprim::exclusive_scan(temp, bytes, f.gone, f.gone_pos, 0u, (size_t)m.n_vox, rocprim::plus<uint32_t>(), st));
+    RUN_TRY(rocprim::exclusive_scan(temp, bytes, f.gone, f.gone_pos, 0u, (size_t)m.n_vox, rocprim::plus<uint32_t>(), st));
     hipLaunchKernelGGL(k_vmap_far_header, dim3(1), dim3(1), 0, st, m, f);
     return hipGetLastError();
 }
@@ -262,7 +247,7 @@ hipError_t vmap_far_commit(const VMapDev& m, const VMapSet& to, const VMapFarArg
 
 hipError_t vmap_rebuild(const VMapDev& m, VMapHeader* hdr, hipStream_t st) {
     if (!m.table) return hipSuccess;
-    VMAP_TRY(hipMemsetAsync(m.table, 0xff, ((size_t)m.table_mask + 1) * sizeof(int32_t), st));
+    RUN_TRY(hipMemsetAsync(m.table, 0xff, ((size_t)m.table_mask + 1) * sizeof(int32_t), st));
     if (m.n_vox == 0) return hipSuccess;
     hipLaunchKernelGGL(k_vmap_rebuild, vmap_grid(m.n_vox), dim3(VOXEL_WG), 0, st, m, hdr);
     return hipGetLastError();
@@ -271,7 +256,7 @@ hipError_t vmap_rebuild(const VMapDev& m, VMapHeader* hdr, hipStream_t st) {
 hipError_t vmap_cloud(const VMapDev& m, uint32_t* pos, double* out, void* temp, size_t temp_bytes, hipStream_t st) {
     if (m.n_vox == 0) return hipSuccess;
     size_t bytes = temp_bytes;
-    VMAP_TRY(rocprim::exclusive_scan(temp, bytes, m.s.count, pos, 0u, (size_t)m.n_vox, rocprim::plus<uint32_t>(), st));
+    RUN_TRY(rocprim::exclusive_scan(temp, bytes, m.s.count, pos, 0u, (size_t)m.n_vox, rocprim::plus<uint32_t>(), st));
     hipLaunchKernelGGL(k_vmap_cloud, vmap_grid((uint64_t)m.n_vox * m.P), dim3(VOXEL_WG), 0, st, m, pos, out);
     return hipGetLastError();
 }

@@ -1,36 +1,21 @@
-// icp_lanes.cpp -- the grid kernels and k_icp_correspond of csrc/k_icp.hip, and the cell table of csrc/k_voxel.hip they build on,
-// compiled for the CPU (tests/cpp/host_lanes/hip/hip_runtime.h: one thread per lane) and driven the way ouster_hip_icp_step drives
-// them; the scan and the stable sort by cell id, which the library takes from rocPRIM, are plain C++ here.  The sum kernels use
-// cross-lane operations and are covered on the GPU only (tests/test_gpu_icp.py).  Built and run by tests/test_icp_lanes_cpu.py,
+// icp_lanes.cpp -- the grid of csrc/k_icp.hip, through the library's own icp_grid_run (and with it voxel_group_run of
+// csrc/k_voxel.hip), and k_icp_correspond, compiled for the CPU (tests/cpp/host_lanes: one thread per lane, rocPRIM's scan and radix
+// sort replaced by stand-ins of the same calling convention) and driven the way ouster_hip_icp_step drives them.  The sum kernels
+// use cross-lane operations and are covered on the GPU only (tests/test_gpu_icp.py).  Built and run by tests/test_icp_lanes_cpu.py,
 // which compares the result with tests/icp_model.py bit for bit.
 //   icp_lanes <case file> <result file>
 // case file: u32 n_src n_tgt src_stride tgt_stride src_n_stride tgt_n_stride f32 plane table_log2 pad, f64 max_corr_dist cos_gate
 // pose[16], then source, target [, source normals, target normals] rows of f32 / f64.  result file: u32 status, u32 cells, then
 // nn i32 [n_src + 16] and r f64 [n_src + 16], both filled with guard values (-77, -7.25) before the run.
-#include "host_lanes/voxel_lanes_atomics.h"
-
-#include <cstring>
-
-inline long long __double_as_longlong(double v) {
-    long long r;
-    std::memcpy(&r, &v, sizeof r);
-    return r;
-}
-
 #include "../../ouster_sdk_amd/csrc/k_voxel.hip"
 #include "../../ouster_sdk_amd/csrc/k_icp.hip"
 
-#include <algorithm>
-#include <cstdio>
-#include <numeric>
-#include <vector>
+#include "host_lanes/lanes_util.h"
 
 namespace ouster_hip_dev {
 int fail_msg(int code, const char*) { return code; }
 }  // namespace ouster_hip_dev
 using namespace ouster_hip_dev;
-
-static bool rd(void* p, size_t bytes, FILE* f) { return bytes == 0 || std::fread(p, 1, bytes, f) == bytes; }
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
@@ -48,12 +33,14 @@ int main(int argc, char** argv) {
     std::fclose(f);
     if (!ok) return 2;
 
-    IcpReadback rb{};
+    // stale content everywhere the run is meant to write before it reads, the read-back and the table included: refusals, and
+    // every slot held by row 0 (a row index in range, so that a run without the reset is refused, not sent on a wild read)
+    IcpReadback rb;
+    std::memset(&rb, 0x5a, sizeof rb);
     const size_t slots = (size_t)1 << table_log2;
-    std::vector<VoxelKey> keys(n_tgt);
-    std::vector<int32_t> table(slots, VOXEL_EMPTY);
-    // stale content everywhere a kernel is meant to write before it reads
-    std::vector<uint32_t> slot(n_tgt, 0xdeadbeefu), first(n_tgt, 7), first_id(n_tgt, 7), vid(n_tgt, 7), idx(n_tgt, 7), svid(n_tgt), sidx(n_tgt),
+    std::vector<VoxelKey> keys(n_tgt, VoxelKey{9, 9, 9, 9});
+    std::vector<int32_t> table(slots, 0);
+    std::vector<uint32_t> slot(n_tgt, 0xdeadbeefu), first(n_tgt, 7), first_id(n_tgt, 7), vid(n_tgt, 7), idx(n_tgt, 7), svid(n_tgt, 7), sidx(n_tgt, 7),
         seg_begin(n_tgt, 0xdeadbeefu), seg_end(n_tgt, 0xdeadbeefu), slot_end(slots, 0xdeadbeefu), flag(n_src, 7);
     std::vector<IcpSlot> islots(slots, IcpSlot{9, 9, 9, 9});
     std::vector<double> rows((size_t)n_tgt * (plane ? 6 : 3), 1e300), xq((size_t)n_src * 6, 1e300), r(n_src + 16, -7.25);
@@ -75,18 +62,10 @@ int main(int argc, char** argv) {
     v.slot = slot.data(), v.first = first.data(), v.first_id = a.first_id, v.vid = vid.data(), v.idx = idx.data();
     v.svid = a.svid, v.sidx = a.sidx, v.seg_begin = a.seg_begin, v.seg_end = a.seg_end;
 
-    if (launch_icp_keys(a, nullptr) != hipSuccess || launch_voxel_insert(v, nullptr) != hipSuccess || launch_voxel_first(v, nullptr) != hipSuccess)
-        return 3;
-    uint32_t s = 0;
-    for (uint32_t i = 0; i < n_tgt; ++i) first_id[i] = s, s += first[i];
-    if (launch_voxel_ids(v, nullptr) != hipSuccess) return 3;
-    std::vector<uint32_t> order(n_tgt);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return vid[x] < vid[y]; });
-    for (uint32_t p = 0; p < n_tgt; ++p) svid[p] = vid[order[p]], sidx[p] = idx[order[p]];
-    if (launch_voxel_segments(v, nullptr) != hipSuccess || launch_icp_slots(a, nullptr) != hipSuccess ||
-        launch_icp_gather(a, nullptr) != hipSuccess)
-        return 3;
+    size_t temp_bytes = 0;
+    if (voxel_temp_bytes(n_tgt, &temp_bytes) != hipSuccess || temp_bytes == 0) return 3;
+    std::vector<uint8_t> temp(temp_bytes);
+    if (icp_grid_run(a, v, temp.data(), temp_bytes, nullptr) != hipSuccess) return 3;
     // like the library, only a clean grid is queried (a refused row would merely be absent from it)
     if (!rb.pass.status && !rb.grid.status) {
         // the device code writes nn / r to the workspace and copies n_src elements out; here they are the outputs themselves
@@ -98,9 +77,9 @@ int main(int argc, char** argv) {
     f = std::fopen(argv[2], "wb");
     if (!f) return 2;
     const uint32_t head[2] = {rb.pass.status | (rb.grid.status << 8), rb.grid.n_vox};
-    std::fwrite(head, sizeof head, 1, f);
-    std::fwrite(nn.data(), 4, nn.size(), f);
-    std::fwrite(r.data(), 8, r.size(), f);
+    wr(head, sizeof head, f);
+    wr(nn.data(), 4 * nn.size(), f);
+    wr(r.data(), 8 * r.size(), f);
     std::fclose(f);
     return 0;
 }

@@ -1,6 +1,6 @@
 // icp_ref_main.cpp -- the host half of ICP (csrc/host/icp_util.cpp, pose_util.cpp) on its own: the reference's two published cases
-// through ouster_hip_icp_align_ref and one pass through ouster_hip_icp_step_ref.  No GPU, no library: `make icp_ref_sanitized` in
-// this directory builds it with -fsanitize=address,undefined, the way to run a sanitizer over that code.
+// through ouster_hip_icp_align_ref and one pass through ouster_hip_icp_step_ref.  No GPU, no library: `make sanitized` in
+// this directory builds it with -fsanitize=address,undefined and runs it, the way to run a sanitizer over that code.
 #include <cmath>
 #include <cstdio>
 #include <string>

@@ -1,5 +1,5 @@
 // icp_target_batch_tool.cpp -- drives hip::DeviceFrameBatch::make_icp_target and align_voxels(IcpTarget) for
-// tests/test_gpu_icp_target_batch.py (built by this directory's icp_target.mk).
+// tests/test_gpu_icp_target_batch.py.
 //   icp_target_batch_tool <capture.pcap> <metadata.json> <n_frames> <voxel_size> <max_corr_dist> <out_prefix>
 // The fixture of icp_batch_tool: two sensors, n_frames double-precision frames from the capture, dewarp(), normals().  Prints
 // "pre_voxel_throws 1" when make_icp_target and align_voxels(target) before any voxel call are std::runtime_error.  Then per route R

@@ -1,5 +1,5 @@
 // icp_target_lanes.cpp -- k_icp_correspond_many of csrc/k_icp.hip compiled for the CPU (tests/cpp/host_lanes/hip/hip_runtime.h: one
-// thread per lane), over a grid built by the library's own grid kernels the way icp_lanes.cpp builds it, a source table and the
+// thread per lane), over a grid built by the library's own icp_grid_run the way icp_lanes.cpp builds it, a source table and the
 // chunk table of csrc/host/icp_util.cpp: several sources against one target in ONE launch, a workgroup per chunk.  Built and run by
 // tests/test_icp_target_lanes_cpu.py, which compares every source's rows with tests/icp_model.py bit for bit.
 //   icp_target_lanes <case file> <result file>
@@ -7,30 +7,15 @@
 // rows [, normals]; then per source u32 n stride n_stride active, f64 pose[16], its rows [, normals].
 // result file: u32 status, u32 chunks, then nn i32 [rows + 16] and r f64 [rows + 16] of the concatenated sources, both filled with
 // guard values (-77, -7.25) before the launch: an inactive source's rows must still hold them afterwards.
-#include "host_lanes/voxel_lanes_atomics.h"
-
-#include <cstring>
-
-inline long long __double_as_longlong(double v) {
-    long long r;
-    std::memcpy(&r, &v, sizeof r);
-    return r;
-}
-
 #include "../../ouster_sdk_amd/csrc/k_voxel.hip"
 #include "../../ouster_sdk_amd/csrc/k_icp.hip"
 
-#include <algorithm>
-#include <cstdio>
-#include <numeric>
-#include <vector>
+#include "host_lanes/lanes_util.h"
 
 namespace ouster_hip_dev {
 int fail_msg(int code, const char*) { return code; }
 }  // namespace ouster_hip_dev
 using namespace ouster_hip_dev;
-
-static bool rd(void* p, size_t bytes, FILE* f) { return bytes == 0 || std::fread(p, 1, bytes, f) == bytes; }
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
@@ -58,12 +43,13 @@ int main(int argc, char** argv) {
     }
     std::fclose(f);
 
-    // the grid, as icp_lanes.cpp builds it
-    IcpReadback rb{};
+    // the grid, as icp_lanes.cpp builds it: the library's icp_grid_run over a workspace full of stale content
+    IcpReadback rb;
+    std::memset(&rb, 0x5a, sizeof rb);
     const size_t slots = (size_t)1 << table_log2;
-    std::vector<VoxelKey> keys(n_tgt);
-    std::vector<int32_t> table(slots, VOXEL_EMPTY);
-    std::vector<uint32_t> slot(n_tgt, 0xdeadbeefu), first(n_tgt, 7), first_id(n_tgt, 7), vid(n_tgt, 7), idx(n_tgt, 7), svid(n_tgt), sidx(n_tgt),
+    std::vector<VoxelKey> keys(n_tgt, VoxelKey{9, 9, 9, 9});
+    std::vector<int32_t> table(slots, 0);   // every slot held by row 0
+    std::vector<uint32_t> slot(n_tgt, 0xdeadbeefu), first(n_tgt, 7), first_id(n_tgt, 7), vid(n_tgt, 7), idx(n_tgt, 7), svid(n_tgt, 7), sidx(n_tgt, 7),
         seg_begin(n_tgt, 0xdeadbeefu), seg_end(n_tgt, 0xdeadbeefu), slot_end(slots, 0xdeadbeefu);
     std::vector<IcpSlot> islots(slots, IcpSlot{9, 9, 9, 9});
     std::vector<double> trows((size_t)n_tgt * (plane ? 6 : 3), 1e300);
@@ -78,18 +64,10 @@ int main(int argc, char** argv) {
     v.n = n_tgt, v.hdr = &rb.grid, v.keys = a.keys, v.table = a.table, v.table_mask = a.table_mask;
     v.slot = slot.data(), v.first = first.data(), v.first_id = a.first_id, v.vid = vid.data(), v.idx = idx.data();
     v.svid = a.svid, v.sidx = a.sidx, v.seg_begin = a.seg_begin, v.seg_end = a.seg_end;
-    if (launch_icp_keys(a, nullptr) != hipSuccess || launch_voxel_insert(v, nullptr) != hipSuccess || launch_voxel_first(v, nullptr) != hipSuccess)
-        return 3;
-    uint32_t s = 0;
-    for (uint32_t i = 0; i < n_tgt; ++i) first_id[i] = s, s += first[i];
-    if (launch_voxel_ids(v, nullptr) != hipSuccess) return 3;
-    std::vector<uint32_t> order(n_tgt);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return vid[x] < vid[y]; });
-    for (uint32_t p = 0; p < n_tgt; ++p) svid[p] = vid[order[p]], sidx[p] = idx[order[p]];
-    if (launch_voxel_segments(v, nullptr) != hipSuccess || launch_icp_slots(a, nullptr) != hipSuccess ||
-        launch_icp_gather(a, nullptr) != hipSuccess)
-        return 3;
+    size_t temp_bytes = 0;
+    if (voxel_temp_bytes(n_tgt, &temp_bytes) != hipSuccess || temp_bytes == 0) return 3;
+    std::vector<uint8_t> temp(temp_bytes);
+    if (icp_grid_run(a, v, temp.data(), temp_bytes, nullptr) != hipSuccess) return 3;
 
     // the two tables of the many-source route, by the library's builder
     const uint64_t n_chunks = icp_chunk_table(rows.data(), n_sources, nullptr, 0, first_row.data(), first_chunk.data());

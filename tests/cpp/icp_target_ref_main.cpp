@@ -1,6 +1,6 @@
 // icp_target_ref_main.cpp -- the plain C++ helpers of the many-source ICP route (csrc/host/icp_util.cpp: the chunk-table builder
 // and the argument checks of ouster_hip_icp_target_*) in a program of its own, built with -fsanitize=address,undefined by
-// `make -C tests/cpp -f icp_target.mk icp_target_ref_sanitized` and run directly.  No GPU, no library.  The chunk tables go into
+// tests/cpp/Makefile (`make -C tests/cpp sanitized` runs it) and run directly.  No GPU, no library.  The chunk tables go into
 // buffers of exactly the size asked for, so a write past a table's end is an ASan report; the table is checked against its
 // definition: every source cut into runs of 1024 rows from its own row 0, sources in order, a source of 0 rows without a chunk.
 #include <cstdio>

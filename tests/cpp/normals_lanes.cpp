@@ -6,14 +6,12 @@
 // xyz, range [, xyz2, range2] [, reduced shifts u32[h]] [, origins f64[w][3] | poses f64[n][w][16], sensor_to_body f64[16]].
 #include "../../ouster_sdk_amd/csrc/k_normals.hip"
 
-#include <cstdio>
+#include "host_lanes/lanes_util.h"
 
 namespace ouster_hip_dev {
 int fail_msg(int code, const char*) { return code; }
 }  // namespace ouster_hip_dev
 using namespace ouster_hip_dev;
-
-static bool rd(void* p, size_t bytes, FILE* f) { return bytes == 0 || std::fread(p, 1, bytes, f) == bytes; }
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;

@@ -1,5 +1,5 @@
 // registration_batch_tool.cpp -- drives hip::DeviceFrameBatch::align_voxels_to_map and mapping::ICPRegistration's device overload for
-// tests/test_gpu_registration_batch.py (built by registration.mk).
+// tests/test_gpu_registration_batch.py.
 //   registration_batch_tool <packets.bin> <h> <w> <n_frames> <known.bin> <k> <out_prefix> <voxel_size> <map_voxel> <max_distance>
 //                           <max_points> <reg_max_distance> <kernel_scale> <max_iterations>
 //       packets.bin, known.bin: as for voxel_batch_tool.cpp, with its two sensors.  Two successive f64 body-frame batches of the same

@@ -2,7 +2,7 @@
 // fold of the thread's rows) and of k_reg_fold (reg_fold_chunks) of csrc/k_registration.hip compiled for the CPU
 // (tests/cpp/host_lanes/hip/hip_runtime.h: one thread per lane).  The wave butterfly of block_sums is device only (__shfl_xor); this
 // program restates it over the threads' accumulators -- the same shape: xor offsets 32 .. 1 within a wave of 64, lane 0 of each wave,
-// the 4 waves in order -- and the chunks go through the kernel's own fold.  Built by registration.mk, run by
+// the 4 waves in order -- and the chunks go through the kernel's own fold.  Built and run by
 // tests/test_registration_lanes_cpu.py, which compares with tests/registration_model.py.
 //   registration_lanes <case file> <result file>
 // case file: u32 n P apply f32 stride n_vox pad pad; f64 voxel_size max_distance kernel_scale; f64 estimate[7]; per voxel i32 cell[3],
@@ -10,25 +10,11 @@
 // filled by linear probing from voxel_hash.
 // result file: f64 moved [n][3]; f64 neighbours [n][3]; f64 dist_sq [n]; f64 terms [n][16]; f64 thread_acc [chunks * 256][16]; f64
 // sums [16]; u64 count; u32 thread_count [chunks * 256]; u8 flags [n].
-#define __constant__ static const
-
 #include "../../ouster_sdk_amd/csrc/k_registration.hip"
 
-#include <cstdio>
-#include <cstring>
-#include <vector>
+#include "host_lanes/lanes_util.h"
 
 using namespace ouster_hip_dev;
-
-static bool rd(void* p, size_t bytes, FILE* f) { return bytes == 0 || std::fread(p, 1, bytes, f) == bytes; }
-static void wr(const void* p, size_t bytes, FILE* f) {
-    if (bytes) std::fwrite(p, 1, bytes, f);
-}
-// the stand-in's launch takes one argument: a kernel of several goes in as a closure, called once per lane
-template <class F>
-static void run(dim3 grid, dim3 wg, F f) {
-    hipLaunchKernelGGL(+[](F* g) { (*g)(); }, grid, wg, 0, nullptr, &f);
-}
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
@@ -77,7 +63,7 @@ int main(int argc, char** argv) {
     a.max_d2 = par[1] * par[1], a.k = par[2];
     a.moved = moved.data(), a.partials = partials.data(), a.counts = counts.data(), a.hdr = &hdr;
     a.flags = flags.data(), a.neighbours = nn.data(), a.dist_sq = d2.data(), a.terms = terms.data();
-    run(dim3(chunks), dim3(ICP_WG), [&] {
+    run_lanes(dim3(chunks), dim3(ICP_WG), [&] {
         double mine[REG_NS];
         uint32_t c;
         if (f32) reg_thread_rows<float>(m, a, blockIdx.x, threadIdx.x, mine, c);
@@ -111,7 +97,7 @@ int main(int argc, char** argv) {
         for (uint32_t w = 1; w < ICP_WG / 64; ++w) pc = pc + c[w * 64];
         counts[b] = pc;
     }
-    run(dim3(1), dim3(64), [&] { reg_fold_chunks(a, chunks, threadIdx.x); });
+    run_lanes(dim3(1), dim3(64), [&] { reg_fold_chunks(a, chunks, threadIdx.x); });
 
     FILE* o = std::fopen(argv[2], "wb");
     if (!o) return 2;

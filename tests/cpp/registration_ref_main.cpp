@@ -1,5 +1,5 @@
 // registration_ref_main.cpp -- the plain C++ half of ICPRegistration (csrc/host/registration_util.cpp over HostVoxelMap of
-// csrc/host/voxel_map_util.cpp) in a program of its own, built with -fsanitize=address,undefined by tests/cpp/registration.mk: the
+// csrc/host/voxel_map_util.cpp) in a program of its own, built with -fsanitize=address,undefined by tests/cpp/Makefile: the
 // checks, the solve, SE(3), the whole loop on empty, tiny, strided and float clouds, rows no cell holds.  No GPU, no library.
 #include <cmath>
 #include <cstdio>

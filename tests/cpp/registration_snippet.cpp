@@ -1,6 +1,6 @@
 // registration_snippet.cpp -- a C++ caller of include/ouster/mapping/icp_registration.h and adaptive_threshold.h on host maps
 // (VoxelHashMap3d::on_host: no GPU): defaults, the reference's scenarios, every refusal.  Built with -Werror by
-// tests/cpp/registration.mk, run by tests/test_registration_api_cpu.py.
+// tests/cpp/Makefile, run by tests/test_registration_api_cpu.py.
 #include <cmath>
 #include <cstdio>
 #include <limits>

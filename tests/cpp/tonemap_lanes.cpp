@@ -6,16 +6,11 @@
 // launch's own choice); n_images ouster_hip_tonemap_params; the input buffer, n_images * in_stride elements; then, unless in place,
 // the output buffer as it is before the call, n_images * out_stride elements of T.
 // result file: the output buffer, luts f32 [n_images][64][1024], hist u32 [n_images][64][1024].
-#include "host_lanes/tonemap_lanes_atomics.h"
-
 #include "../../ouster_sdk_amd/csrc/k_tonemap.hip"
 
-#include <cstdio>
-#include <vector>
+#include "host_lanes/lanes_util.h"
 
 using namespace ouster_hip_dev;
-
-static bool rd(void* p, size_t bytes, FILE* f) { return bytes == 0 || std::fread(p, 1, bytes, f) == bytes; }
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;

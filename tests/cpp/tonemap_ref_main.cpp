@@ -1,7 +1,7 @@
 // tonemap_ref_main.cpp -- the host half of the display images (csrc/host/image_processing.cpp) on its own: the state machines of
 // LocalToneMapper, AutoExposure and BeamUniformityCorrector driven through step() over a brightness sweep, and update() against a
 // device half that refuses, as it does without a GPU.  No GPU, no library: the C ABI calls the file makes are stubs here.
-// `make tonemap_ref_sanitized` in this directory builds it with -fsanitize=address,undefined and runs it, the way to run a
+// `make sanitized` in this directory builds it with -fsanitize=address,undefined and runs it with the others of its kind, the way to run a
 // sanitizer over that code.
 #include <cmath>
 #include <cstdio>

@@ -1,31 +1,19 @@
-// voxel_lanes.cpp -- csrc/k_voxel.hip compiled for the CPU (tests/cpp/host_lanes/hip/hip_runtime.h: one thread per lane) and driven
-// the way ouster_hip_voxel_downsample drives it; the two scans and the stable sort by voxel id, which the library takes from rocPRIM,
-// are plain C++ here.  Built and run by tests/test_voxel_lanes_cpu.py, which compares the result with tests/voxel_model.py bit for
-// bit.
+// voxel_lanes.cpp -- csrc/k_voxel.hip compiled for the CPU (tests/cpp/host_lanes: one thread per lane, rocPRIM's scan and radix sort
+// replaced by stand-ins of the same calling convention) and run through the library's own voxel_run, the function
+// ouster_hip_voxel_downsample calls: the reset, the order of the steps and the width of the sort are the library's.  Built and run
+// by tests/test_voxel_lanes_cpu.py, which compares the result with tests/voxel_model.py bit for bit.
 //   voxel_lanes <case file> <result file>
 // case file: u32 n cols stride f32 form table_log2, f64 voxel_size, u64 min_pts capacity, points [n][stride] of f32 / f64
 // [, normals f64 [n][3] when form == 3].  result file: u32 status n_vox, u64 n_out, out f64 [capacity][cols], out_normals f64
 // [capacity][3], both filled with -7.25 before the run.
-#include "host_lanes/voxel_lanes_atomics.h"
-
 #include "../../ouster_sdk_amd/csrc/k_voxel.hip"
 
-#include <algorithm>
-#include <cstdio>
-#include <numeric>
-#include <vector>
+#include "host_lanes/lanes_util.h"
 
 namespace ouster_hip_dev {
 int fail_msg(int code, const char*) { return code; }
 }  // namespace ouster_hip_dev
 using namespace ouster_hip_dev;
-
-static bool rd(void* p, size_t bytes, FILE* f) { return bytes == 0 || std::fread(p, 1, bytes, f) == bytes; }
-
-static void exclusive_scan(const std::vector<uint32_t>& in, std::vector<uint32_t>& out) {
-    uint32_t s = 0;
-    for (size_t i = 0; i < in.size(); ++i) out[i] = s, s += in[i];
-}
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
@@ -44,11 +32,12 @@ int main(int argc, char** argv) {
     if (!ok) return 2;
 
     const bool folds = form == VOXEL_FORM_AVERAGE || form == VOXEL_FORM_NORMALS;
-    VoxelHeader hdr{};
-    std::vector<VoxelKey> keys(n);
-    std::vector<int32_t> table((size_t)1 << table_log2, VOXEL_EMPTY);
-    // stale content everywhere a kernel is meant to write before it reads
-    std::vector<uint32_t> slot(n, 0xdeadbeefu), first(n, 7), first_id(n, 7), vid(n, 7), idx(n, 7), svid(n), sidx(n), seg_begin(n, 0xdeadbeefu),
+    // stale content everywhere the run is meant to write before it reads, the header and the table included: a refusal, and
+    // every slot held by row 0 (a row index in range, so that a run without the reset is refused, not sent on a wild read)
+    VoxelHeader hdr{VOXEL_STATUS_TABLE, 0xdeadbeefu, 0xdeadbeefdeadbeefull};
+    std::vector<VoxelKey> keys(n, VoxelKey{9, 9, 9, 9});
+    std::vector<int32_t> table((size_t)1 << table_log2, 0);
+    std::vector<uint32_t> slot(n, 0xdeadbeefu), first(n, 7), first_id(n, 7), vid(n, 7), idx(n, 7), svid(n, 7), sidx(n, 7), seg_begin(n, 0xdeadbeefu),
         seg_end(n, 0xdeadbeefu), keep(n, 7), pos(n, 7);
     std::vector<double> rows(folds ? (size_t)n * (form == VOXEL_FORM_NORMALS ? 6 : cols) : 0, 1e300);
     std::vector<double> out((size_t)cap * cols, -7.25), out_n((size_t)cap * 3, -7.25);
@@ -62,27 +51,16 @@ int main(int argc, char** argv) {
     a.seg_begin = seg_begin.data(), a.seg_end = seg_end.data(), a.rows = rows.data(), a.keep = keep.data(), a.pos = pos.data();
     a.out = out.data(), a.out_normals = out_n.data(), a.out_capacity = cap;
 
-    if (launch_voxel_keys(a, nullptr) != hipSuccess || launch_voxel_insert(a, nullptr) != hipSuccess ||
-        launch_voxel_first(a, nullptr) != hipSuccess)
-        return 3;
-    exclusive_scan(first, first_id);
-    if (launch_voxel_ids(a, nullptr) != hipSuccess) return 3;
-    std::vector<uint32_t> order(n);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return vid[x] < vid[y]; });
-    for (uint32_t p = 0; p < n; ++p) svid[p] = vid[order[p]], sidx[p] = idx[order[p]];
-    if (launch_voxel_segments(a, nullptr) != hipSuccess) return 3;
-    if (folds) {
-        if (launch_voxel_gather(a, nullptr) != hipSuccess || launch_voxel_reduce(a, nullptr) != hipSuccess) return 3;
-        exclusive_scan(keep, pos);
-    }
-    if (launch_voxel_write(a, nullptr) != hipSuccess) return 3;
+    size_t temp_bytes = 0;
+    if (voxel_temp_bytes(n, &temp_bytes) != hipSuccess || temp_bytes == 0) return 3;
+    std::vector<uint8_t> temp(temp_bytes);
+    if (voxel_run(a, temp.data(), temp_bytes, nullptr) != hipSuccess) return 3;
 
     f = std::fopen(argv[2], "wb");
     if (!f) return 2;
-    std::fwrite(&hdr, sizeof hdr, 1, f);
-    std::fwrite(out.data(), 8, out.size(), f);
-    std::fwrite(out_n.data(), 8, out_n.size(), f);
+    wr(&hdr, sizeof hdr, f);
+    wr(out.data(), 8 * out.size(), f);
+    wr(out_n.data(), 8 * out_n.size(), f);
     std::fclose(f);
     return 0;
 }

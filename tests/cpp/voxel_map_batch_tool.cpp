@@ -1,5 +1,5 @@
 // voxel_map_batch_tool.cpp -- drives add_voxels_to / update_voxel_map / closest_in / map_neighbors_device / download_map_neighbors of
-// hip::DeviceFrameBatch for tests/test_gpu_voxel_map_batch.py (built by voxel_map.mk).
+// hip::DeviceFrameBatch for tests/test_gpu_voxel_map_batch.py.
 //   voxel_map_batch_tool <packets.bin> <h> <w> <n_frames> <known.bin> <k> <out_prefix> <voxel_size> <map_voxel> <max_distance> <max_points> <bound_sq>
 //       packets.bin, known.bin: as for voxel_batch_tool.cpp, with its two sensors.  Three successive f64 body-frame batches r = 0, 1,
 //       2 of the same packets, batch r with its known poses moved by r * (1.5, -0.75, 0.25) m and packet r of frame r left out; each

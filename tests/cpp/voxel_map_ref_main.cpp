@@ -1,5 +1,5 @@
 // voxel_map_ref_main.cpp -- the plain C++ half of the voxel map (csrc/host/voxel_map_util.cpp) in a program of its own, built with
-// -fsanitize=address,undefined by tests/cpp/voxel_map.mk: validation, every operation of HostVoxelMap against a brute-force search
+// -fsanitize=address,undefined by tests/cpp/Makefile: validation, every operation of HostVoxelMap against a brute-force search
 // and against its own bookkeeping, at the edges of the int32 grid.  No GPU, no library.
 #include <cmath>
 #include <cstdio>

@@ -3,8 +3,6 @@ test_gpu_icp_target.py), all over tests/icp_cases.py: the two step groups, the s
 each, and the ouster_hip_icp_target_* calls through ctypes."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
@@ -12,28 +10,6 @@ import icp_cases as K
 import icp_model as M
 
 CHUNK = 1024
-
-
-# ---- the C++ programs: tests/cpp/icp_target.mk, a makefile of its own over the variables of tests/cpp/Makefile ------------------
-def build(name):
-    """make -C tests/cpp -f icp_target.mk _build/<name> -> (path of the executable, environment to run it with), like cpp_tools.build"""
-    import cpp_tools
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    cpp, lib = os.path.join(cpp_tools.ROOT, "tests", "cpp"), os.path.join(cpp_tools.ROOT, "ouster_sdk_amd", "lib")
-    p = subprocess.run(["make", "-C", cpp, "-f", "icp_target.mk", "_build/" + name, "CXX=" + os.environ.get("CXX", "g++"), "ROCM=" + rocm],
-                       capture_output=True, text=True)
-    assert p.returncode == 0, "make -f icp_target.mk _build/%s failed:\n%s" % (name, (p.stdout + p.stderr)[-3000:])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    return os.path.join(cpp, "_build", name), env
-
-
-def run(name, args, timeout=600):
-    """builds <name> and runs it with args, which must succeed -> the CompletedProcess, like cpp_tools.run"""
-    exe, env = build(name)
-    p = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, env=env, timeout=timeout)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    return p
 
 
 # ---- step: two groups, each one call.  (target case, [(n, variant)], the pose every source starts from) -----------------------------

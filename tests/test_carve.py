@@ -5,20 +5,14 @@ of 1, 255, 256 and 257 bytes, a piece of 2^31 + 1 bytes that is counted and neve
 256-byte aligned, that pieces do not overlap, that the last one ends within the total, and that the measuring and the
 assigning pass agree on the total.  tests/cpp/Makefile also builds it with the address and undefined-behaviour sanitizers
 (_build/test_carve_san); this wrapper runs the plain build."""
-import os
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOL = os.path.join(ROOT, "tests", "cpp", "_build", "test_carve")
+import cpp_tools
 
 
 def _tool():
-    """tests/cpp/_build/test_carve.  build() makes it; a tests/ directory put in place after the build has none, and makes it
-    here by the same rule of tests/cpp/Makefile (g++ only)."""
-    if not os.path.exists(TOOL):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s", "_build/test_carve"])
-    assert os.path.exists(TOOL), "tests/cpp/_build/test_carve is missing: build() makes it"
-    return TOOL
+    """tests/cpp/_build/test_carve, by the rule of tests/cpp/Makefile (g++ only): build() makes it, and this brings it up to date"""
+    return cpp_tools.build("test_carve")[0]
 
 
 def test_carve_layouts():

@@ -6,17 +6,13 @@ import subprocess
 
 import pytest
 
-from conftest import ROOT
+import cpp_tools
 
 pytestmark = pytest.mark.gpu
 
 
 def test_cpp_core_api():
-    exe = os.path.join(ROOT, "tests", "cpp", "_build", "test_core_api")
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s"])  # g++ only, incremental
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.join(ROOT, "ouster_sdk_amd", "lib") + ":/opt/rocm/lib:" + \
-        env.get("LD_LIBRARY_PATH", "")
+    exe, env = cpp_tools.build("test_core_api")  # g++ only, incremental
     p = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=600)
     print(p.stdout[-4000:])
     print(p.stderr[-2000:])
@@ -29,12 +25,8 @@ def test_eigen_boundary_switch_compiles_and_runs(switch):
     """include/ouster/core/typedefs.h with and without -DOUSTER_HIP_USE_EIGEN: the reference-style
     snippet (Field -> image -> destagger -> cartesian) builds and gives the same answers both ways.
     (Eigen3 is mocked by tests/cpp/mock_eigen: it is not installed in this image.)"""
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s"])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.join(ROOT, "ouster_sdk_amd", "lib") + ":/opt/rocm/lib:" + \
-        env.get("LD_LIBRARY_PATH", "")
-    exe = os.path.join(ROOT, "tests", "cpp", "_build", "eigen_switch_" + switch)
-    p = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
+    exe, env = cpp_tools.build("eigen_switch_" + switch)
+    p =subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode == 0 and "0 mismatches" in p.stdout, p.stdout + p.stderr[-2000:]
 
 
@@ -44,11 +36,7 @@ def test_reference_snapshot_hashes_through_cpp_mirror(oracle):
     import json
     from conftest import GOLDEN, PCAPS
     O = oracle
-    exe = os.path.join(ROOT, "tests", "cpp", "_build", "snapshot_tool")
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s"])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.join(ROOT, "ouster_sdk_amd", "lib") + ":/opt/rocm/lib:" + \
-        env.get("LD_LIBRARY_PATH", "")
+    exe, env = cpp_tools.build("snapshot_tool")
     snaps = json.load(open(os.path.join(GOLDEN, "snapshot_hashes.json")))
     names = {v: k for k, v in O.PROFILES.items()}
     assert len(snaps) == 5

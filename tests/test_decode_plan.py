@@ -10,8 +10,9 @@ import subprocess
 
 import pytest
 
+import cpp_tools
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOL = os.path.join(ROOT, "tests", "cpp", "_build", "plan_tool")
 TABLE = os.path.join(ROOT, "tests", "golden", "decode_plans.json")
 
 
@@ -44,12 +45,8 @@ def rows():
 
 
 def _tool():
-    """tests/cpp/_build/plan_tool.  build() makes it; a tests/ directory put in place after the build has none, and makes it here
-    by the same rule of tests/cpp/Makefile (g++ only)."""
-    if not os.path.exists(TOOL):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s", "_build/plan_tool"])
-    assert os.path.exists(TOOL), "tests/cpp/_build/plan_tool is missing: build() makes it"
-    return TOOL
+    """tests/cpp/_build/plan_tool, by the rule of tests/cpp/Makefile (g++ only): build() makes it, and this brings it up to date"""
+    return cpp_tools.build("plan_tool")[0]
 
 
 @pytest.fixture(scope="module")

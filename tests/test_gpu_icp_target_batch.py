@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import cpp_tools
 import icp_target_cases as T
 from conftest import PCAPS, has_gpu
 
@@ -24,7 +25,7 @@ DIST = 0.5
 def run(tmp_path_factory):
     assert has_gpu()
     tmp = tmp_path_factory.mktemp("icp_target_batch")
-    res = T.run("icp_target_batch_tool", [os.path.join(PCAPS, "OS-1-128_v2.3.0_1024x10_lb_n3.pcap"),
+    res = cpp_tools.run("icp_target_batch_tool", [os.path.join(PCAPS, "OS-1-128_v2.3.0_1024x10_lb_n3.pcap"),
                                                   os.path.join(PCAPS, "OS-1-128_v2.3.0_1024x10.json"), N_FRAMES, VOXEL, DIST, tmp / "o"], timeout=300)
     out = {"stdout": res.stdout}
     for route in ("plane", "point"):

@@ -4,32 +4,20 @@ the same packets with its poses moved on by centimetres is aligned with align_vo
 and it is aligned again against the grown map.  Both poses must equal ouster_hip_registration_align on the batches' OWN
 download_voxels rows bit for bit.  The refusals: before voxel_downsample (std::runtime_error), a map that lives on no device
 (std::invalid_argument), a negative max_distance."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import batch_cases as B
+import cpp_tools
 import registration_cases as K
 import voxel_map_cases as VK
 from batch_cases import H, N, W
-from conftest import ROOT, has_gpu
+from conftest import has_gpu
 
 pytestmark = pytest.mark.gpu
 
 VOXEL, MAP_VOXEL, MAX_DISTANCE, MAX_POINTS = 0.25, 1.0, 300.0, 3        # the scene spans several hundred metres
 REG_DISTANCE, KERNEL, ITERATIONS = 1.0, 0.3, 30
-
-
-def build(name):
-    cpp, lib = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "ouster_sdk_amd", "lib")
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    p = subprocess.run(["make", "-C", cpp, "-f", "registration.mk", "-s", "_build/" + name], capture_output=True, text=True)
-    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    return os.path.join(cpp, "_build", name), env
 
 
 @pytest.fixture(scope="module")
@@ -38,11 +26,9 @@ def run(oracle, tmp_path_factory):
     tmp = tmp_path_factory.mktemp("registration_batch")
     B.write_packets(oracle, tmp, B.scene)
     B.write_known(tmp)
-    exe, env = build("registration_batch_tool")
     args = [tmp / "packets.bin", H, W, N, tmp / "known.bin", B.K, tmp / "o", VOXEL, MAP_VOXEL, MAX_DISTANCE, MAX_POINTS, REG_DISTANCE, KERNEL,
             ITERATIONS]
-    p = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    p = cpp_tools.run("registration_batch_tool", args)
     out = {"stdout": p.stdout}
     for name in ("r0.vox", "r1.vox", "corrected"):
         out[name] = np.fromfile(tmp / ("o." + name), np.float64).reshape(-1, 3)

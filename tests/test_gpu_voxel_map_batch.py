@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import batch_cases as B
+import cpp_tools
 import voxel_map_cases as K
 import voxel_map_model as M
 from batch_cases import H, N, W
@@ -21,15 +22,12 @@ STEP = np.array([1.5, -0.75, 0.25])
 
 @pytest.fixture(scope="module")
 def run(oracle, tmp_path_factory):
-    import subprocess
     assert has_gpu()
     tmp = tmp_path_factory.mktemp("voxel_map_batch")
     B.write_packets(oracle, tmp, B.scene)
     B.write_known(tmp)
-    exe, env = K.build("voxel_map_batch_tool")
     args = [tmp / "packets.bin", H, W, N, tmp / "known.bin", B.K, tmp / "o", VOXEL, MAP_VOXEL, MAX_DISTANCE, MAX_POINTS, BOUND_SQ]
-    p = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    p = cpp_tools.run("voxel_map_batch_tool", args)
     out = {"stdout": p.stdout}
     for r in range(3):
         for name in ("vox", "cloud", "pos"):

@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import cpp_tools
 import icp_cases as K
 import icp_model as M
 import icp_target_cases as T
@@ -267,16 +268,16 @@ def test_python_face_names_defaults_and_errors():
 
 
 def test_cpp_caller_compiles_links_and_runs():
-    """tests/cpp/icp_target_snippet.cpp, built by tests/cpp/icp_target.mk with the flags of the other C++ tests and -Werror"""
-    p = T.run("icp_target_snippet", [], timeout=300)
+    """tests/cpp/icp_target_snippet.cpp, built by tests/cpp/Makefile with the flags of the other C++ callers (-Werror)"""
+    p = cpp_tools.run("icp_target_snippet", [], timeout=300)
     assert "validation ok" in p.stdout and "small targets ok" in p.stdout, p.stdout
     assert p.stdout.splitlines()[-1].startswith("ok" if has_gpu() else "no-gpu"), p.stdout
 
 
 def test_host_helpers_under_the_sanitizers():
     """tests/cpp/icp_target_ref_main.cpp: the chunk-table builder and the argument checks in a program of their own, built with
-    -fsanitize=address,undefined (make -C tests/cpp -f icp_target.mk icp_target_ref_sanitized) and run directly"""
-    exe = T.build("icp_target_ref_sanitized")[0]
+    -fsanitize=address,undefined (tests/cpp/Makefile: _build/icp_target_ref_sanitized) and run directly"""
+    exe = cpp_tools.build("icp_target_ref_sanitized")[0]
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and p.stdout.strip().endswith("icp_target_ref_main: ok"), p.stdout + p.stderr
 

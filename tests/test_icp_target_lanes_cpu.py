@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cpp_tools
 import icp_cases as K
 import icp_model as M
 import icp_target_cases as T
@@ -19,7 +20,7 @@ import icp_target_cases as T
 
 @pytest.fixture(scope="module")
 def lanes():
-    return T.build("icp_target_lanes")[0]
+    return cpp_tools.build("icp_target_lanes")[0]
 
 
 def run(exe, tmp_path, group, plane, active, angle):

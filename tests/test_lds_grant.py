@@ -6,22 +6,16 @@ asked at or below 48 KB, that the first request above it asks and an equal or sm
 asks again, that devices 0 and 1 are independent, and that devices 16 and -1 are never remembered and never read device 0's
 slot.  tests/cpp/Makefile also builds it with the address and undefined-behaviour sanitizers (_build/test_lds_grant_san, a
 stand-alone program); both builds are run here."""
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cpp_tools
 
 
 def _tool(name):
-    """tests/cpp/_build/<name>.  build() makes it; a tests/ directory put in place after the build has none, and makes it
-    here by the same rule of tests/cpp/Makefile (g++ only)."""
-    tool = os.path.join(ROOT, "tests", "cpp", "_build", name)
-    if not os.path.exists(tool):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s", "_build/" + name])
-    assert os.path.exists(tool), "tests/cpp/_build/%s is missing: build() makes it" % name
-    return tool
+    """tests/cpp/_build/<name>, by the rule of tests/cpp/Makefile (g++ only): build() makes it, and this brings it up to date"""
+    return cpp_tools.build(name)[0]
 
 
 @pytest.mark.parametrize("name", ["test_lds_grant", "test_lds_grant_san"])

@@ -4,12 +4,12 @@ reference's Python scenarios through ouster.sdk.mapping.  No GPU."""
 import ctypes as C
 import math
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import cpp_tools
 import registration_cases as K
 import registration_model as R
 import voxel_map_cases as VK
@@ -164,11 +164,7 @@ def test_refusals_through_python():
 
 
 def test_refusals_through_cpp():
-    exe = os.path.join(ROOT, "tests", "cpp", "_build", "registration_snippet")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-f", "registration.mk", "-s", "_build/registration_snippet"])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = cpp_tools.run("registration_snippet", [], timeout=60)
     assert "registration_snippet: ok" in out.stdout
 
 

@@ -4,23 +4,15 @@ squared distances and terms bit for bit; every thread's accumulators are the lef
 thread-to-row mapping); the sums within (ceil(N / 1024) + 40) * 2^-53 * sum |t| of math.fsum of the terms and the count exact.  The
 inputs are those of tests/registration_cases.py.  No GPU."""
 import math
-import os
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_tools
 import registration_cases as K
 import registration_model as R
-from conftest import ROOT
-
-
-def build():
-    cpp = os.path.join(ROOT, "tests", "cpp")
-    p = subprocess.run(["make", "-C", cpp, "-f", "registration.mk", "-s", "_build/registration_lanes"], capture_output=True, text=True)
-    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
-    return os.path.join(cpp, "_build", "registration_lanes")
 
 
 def run_lanes(tmp_path, rows, dtype, stride, estimate, P):
@@ -40,7 +32,7 @@ def run_lanes(tmp_path, rows, dtype, stride, estimate, P):
             pts[v, :len(bucket)] = bucket
         f.write(pts.tobytes())
         f.write(a.tobytes())
-    p = subprocess.run([build(), str(case), str(result)], capture_output=True, text=True, timeout=600)
+    p = subprocess.run([cpp_tools.build("registration_lanes")[0], str(case), str(result)], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and p.stdout.strip() == "registration_lanes: done", (p.returncode, p.stdout, p.stderr)
     raw, at, out = open(result, "rb").read(), 0, {}
     threads = math.ceil(n / 1024) * 256

@@ -1,6 +1,5 @@
 """CPU-only: k_tm_hist, k_tm_luts and k_tm_finish of csrc/k_tonemap.hip compiled for the host, one thread per lane and 64 lanes per
-workgroup (tests/cpp/tonemap_lanes.cpp over tests/cpp/host_lanes/hip/hip_runtime.h, with the integer atomic of
-host_lanes/tonemap_lanes_atomics.h), against tests/tonemap_model.py bit for bit: the counts, the tables and the images.  It checks
+workgroup (tests/cpp/tonemap_lanes.cpp over tests/cpp/host_lanes/hip/hip_runtime.h, whose integer atomics are real ones), against tests/tonemap_model.py bit for bit: the counts, the tables and the images.  It checks
 what can go wrong without a GPU in sight -- tile bounds, the order of the float sums, the extrapolating blend, rows that change
 inside a lane's four pixels, strides, in place and out of place; the device's own arithmetic and the C ABI around the kernels are
 tests/test_gpu_tonemap.py's business."""

@@ -7,22 +7,16 @@ to the earlier candidate; no usable sample, no win; nothing usable, 256), the ca
 the round trip through a file, `retune`, the bound on the table, that every route by which an entry goes destroys its
 samples, and that another candidate list under the same key starts over.  tests/cpp/Makefile also builds it with the address
 and undefined-behaviour sanitizers (_build/test_tuner_san, a stand-alone program); both builds are run here."""
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cpp_tools
 
 
 def _tool(name):
-    """tests/cpp/_build/<name>.  build() makes it; a tests/ directory put in place after the build has none, and makes it
-    here by the same rule of tests/cpp/Makefile (g++ only)."""
-    tool = os.path.join(ROOT, "tests", "cpp", "_build", name)
-    if not os.path.exists(tool):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s", "_build/" + name])
-    assert os.path.exists(tool), "tests/cpp/_build/%s is missing: build() makes it" % name
-    return tool
+    """tests/cpp/_build/<name>, by the rule of tests/cpp/Makefile (g++ only): build() makes it, and this brings it up to date"""
+    return cpp_tools.build(name)[0]
 
 
 @pytest.mark.parametrize("name", ["test_tuner", "test_tuner_san"])

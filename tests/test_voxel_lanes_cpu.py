@@ -1,10 +1,13 @@
 """CPU-only: the source of the voxel kernels (csrc/k_voxel.hip) compiled for the host, one thread per lane (tests/cpp/voxel_lanes.cpp
-over tests/cpp/host_lanes/hip/hip_runtime.h, with the two integer atomics of host_lanes/voxel_lanes_atomics.h), against
-tests/voxel_model.py bit for bit, row order included.  Keys, hash insert (real threads race for the slots), ids, segments, gather,
-reduce and write are the library's source; the scans and the stable sort, rocPRIM's on the device, are plain C++ here.  It checks
-what can go wrong without a GPU in sight -- the validity rules, the floor at negative coordinates, the order of every sum, strides,
-the compaction, what a refusal leaves behind; the device's own arithmetic and the C ABI around the kernels are
-tests/test_gpu_voxel.py's business."""
+over tests/cpp/host_lanes), against tests/voxel_model.py bit for bit, row order included.  The program calls the library's own
+voxel_run: keys, hash insert (real threads race for the slots), ids, segments, gather, reduce and write are the library's source,
+and so are the resets, the order of the steps and the number of bits the sort is given; only the two rocPRIM calls themselves are
+stand-ins (a scan, and a stable sort that looks at the key bits it is given and no others).  It checks what can go wrong without a
+GPU in sight -- the validity rules, the floor at negative coordinates, the order of every sum, strides, the compaction, what a
+refusal leaves behind, the width of the sort; the device's own arithmetic and the C ABI around the kernels are
+tests/test_gpu_voxel.py's business.
+A stale workspace needs no test of its own: the program fills the header, the hash table (every slot held by row 0) and every other
+array with junk before each run, so every case here of more than one voxel passes only if voxel_run resets what it must."""
 import struct
 import subprocess
 
@@ -135,3 +138,51 @@ def test_refusals_write_nothing(lanes, tmp_path):
         status, _, n_out, out, _ = run(lanes, tmp_path, cloud, 1.0, form, capacity=3)
         assert status == 0 and n_out == 4 == len(K.want(cloud, 1.0, strategy=strategy)) and (out == K.GUARD).all()
         same(run(lanes, tmp_path, cloud, 1.0, form, capacity=4), K.want(cloud, 1.0, strategy=strategy), 3, "capacity 4")
+
+
+# ---- the width of the sort: voxel_sort_bits(n) bits hold the ids 0 .. n; 255, 256 and 257 rows lie around the step from 8 to 9
+def own_voxels(n, cols=4):
+    """n rows, row i alone in voxel (i, 0, 0) of a voxel-1.0 grid: voxel ids 0 .. n - 1 in row order"""
+    c = np.random.default_rng(n).uniform(0.05, 0.95, (n, cols))
+    c[:, 0] += np.arange(n)
+    return c
+
+
+@pytest.mark.parametrize("n", [255, 256, 257])
+def test_sort_width_every_row_a_voxel_of_its_own(lanes, tmp_path, n):
+    """ids up to n - 1: with 255 rows they use the top bit of the 8-bit key.  On its own this order of ids cannot go wrong -- a
+    voxel of one row is one segment wherever the sort puts it -- so the two tests below bring rows that a narrower sort tears apart"""
+    cloud = own_voxels(n)
+    for form, strategy in ((FORM_FIRST, M.FIRST_N_POINT), (FORM_AVERAGE, M.AVERAGE_POINT)):
+        got = run(lanes, tmp_path, cloud, 1.0, form)
+        same(got, K.want(cloud, 1.0, strategy=strategy), 4, "%d voxels of one row, form %d" % (n, form))
+        assert got[1] == n
+
+
+def test_sort_width_voxels_that_differ_in_the_top_bit_only(lanes, tmp_path):
+    """255 rows, an 8-bit key: rows 0 .. 199 open voxels 0 .. 199, then voxels 0, 128, 1, 129, ... get a second row each.  A sort
+    blind to bit 7 takes ids k and 128 + k for one and leaves their rows interleaved: k, 128 + k, k, 128 + k"""
+    first = own_voxels(200)
+    again = first[[k // 2 + 128 * (k % 2) for k in range(55)]] * [1.0, 0.5, 0.5, -3.0]     # the same cells, other rows
+    cloud = np.vstack([first, again])
+    assert len(cloud) == 255
+    for form, strategy in ((FORM_FIRST, M.FIRST_N_POINT), (FORM_LAST, M.RANDOM), (FORM_AVERAGE, M.AVERAGE_POINT)):
+        got = run(lanes, tmp_path, cloud, 1.0, form)
+        same(got, K.want(cloud, 1.0, strategy=strategy), 4, "aliased ids, form %d" % form)
+        assert got[1] == 200
+
+
+@pytest.mark.parametrize("n", [256, 257])
+def test_sort_width_a_skipped_row_has_the_largest_key(lanes, tmp_path, n):
+    """With 256 and 257 rows the key has 9 bits, and bit 8 is set in one id only that these rows can produce together with a
+    second row per voxel: n itself, the id of a row that takes no part.  Rows: voxel 0, voxel 1, a row with a zero normal, voxel 0
+    again, voxel 1 again, then a voxel per row.  A sort blind to bit 8 reads 256 as 0 and 257 as 1, and puts the skipped row
+    between the two rows of that voxel"""
+    pts = own_voxels(n - 3, 3)
+    pts = np.vstack([pts[:2], [[0.5, 0.5, 0.5]], pts[:2] * [1.0, 0.5, 0.5], pts[2:]])
+    nrm = np.random.default_rng(n).normal(size=(n, 3))
+    nrm[2] = 0.0
+    assert len(pts) == n
+    got = run(lanes, tmp_path, pts, 1.0, FORM_NORMALS, normals=nrm)
+    same(got, K.want(pts, 1.0, normals=nrm), 3, "%d rows, one skipped" % n)
+    assert got[1] == n - 3

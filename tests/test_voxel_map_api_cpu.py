@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import cpp_tools
 import voxel_map_cases as K
 import voxel_map_model as M
 from conftest import ROOT, has_gpu
@@ -25,9 +26,6 @@ MSG_CAPACITY = "voxel map: out_capacity is too small"
 
 def last_error():
     return capi.load_hip().ouster_hip_last_error().decode()
-
-
-build = K.build
 
 
 def host_map(*a, **kw):
@@ -230,17 +228,15 @@ def test_python_face_names_defaults_and_errors():
 
 
 def test_cpp_caller_compiles_links_and_runs():
-    """tests/cpp/voxel_map_snippet.cpp, built by tests/cpp/voxel_map.mk with the flags of the other C++ tests and -Werror"""
-    exe, env = build("voxel_map_snippet")
-    p = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    """tests/cpp/voxel_map_snippet.cpp, built by tests/cpp/Makefile with the flags of the other C++ callers (-Werror)"""
+    p = cpp_tools.run("voxel_map_snippet", [], timeout=300)
     assert "validation ok" in p.stdout and "host map ok" in p.stdout, p.stdout
     assert p.stdout.splitlines()[-1].startswith("ok" if has_gpu() else "no-gpu"), p.stdout
 
 
 def test_host_half_under_the_sanitizers():
     """tests/cpp/voxel_map_ref_main.cpp: csrc/host/voxel_map_util.cpp in a program of its own, built with
-    -fsanitize=address,undefined (make -C tests/cpp -f voxel_map.mk voxel_map_ref_sanitized) and run directly"""
-    exe = build("voxel_map_ref_sanitized")[0]
+    -fsanitize=address,undefined (tests/cpp/Makefile: _build/voxel_map_ref_sanitized) and run directly"""
+    exe = cpp_tools.build("voxel_map_ref_sanitized")[0]
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and p.stdout.strip().endswith("voxel_map_ref_main: ok"), p.stdout + p.stderr

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cpp_tools
 import voxel_map_cases as K
 import voxel_map_model as M
 
@@ -22,7 +23,7 @@ def run_lanes(tmp_path, calls, queries, voxel_size, max_distance, max_points, bo
             f.write(struct.pack("<2I", len(rows), 0))
             f.write(rows.tobytes())
         f.write(queries.tobytes())
-    exe = K.build("voxel_map_lanes")[0]
+    exe = cpp_tools.build("voxel_map_lanes")[0]
     p = subprocess.run([exe, str(case), str(result)], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and p.stdout.strip() == "voxel_map_lanes: done", (p.returncode, p.stdout, p.stderr)
     raw = open(result, "rb").read()

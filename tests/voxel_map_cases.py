@@ -3,15 +3,12 @@ tests/test_voxel_map_api_cpu.py and tests/test_gpu_voxel_map.py run them through
 model's method names, with guard rows behind every output -- and the script runner both sides go through."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
 import voxel_map_model as M
 
 F32, F64 = 9, 10   # OUSTER_HIP_F32 / OUSTER_HIP_F64 (include/ouster_hip.h)
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = 3         # rows before and behind every output that must keep their sentinel
 SENTINEL = -12345.678
 
@@ -22,19 +19,6 @@ def next_down(x):
 
 def next_up(x):
     return float(np.nextafter(x, np.inf))
-
-
-# ---- the C++ programs of tests/cpp/voxel_map.mk
-def build(name):
-    """make -C tests/cpp -f voxel_map.mk _build/<name> -> (path of the executable, environment to run it with)"""
-    rocm = os.environ.get("ROCM", "/opt/rocm")
-    cpp, lib = os.path.join(REPO, "tests", "cpp"), os.path.join(REPO, "ouster_sdk_amd", "lib")
-    p = subprocess.run(["make", "-C", cpp, "-f", "voxel_map.mk", "_build/" + name, "CXX=" + os.environ.get("CXX", "g++"), "ROCM=" + rocm],
-                       capture_output=True, text=True)
-    assert p.returncode == 0, "make -f voxel_map.mk _build/%s failed:\n%s" % (name, (p.stdout + p.stderr)[-3000:])
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = lib + ":" + os.path.join(rocm, "lib") + ":" + env.get("LD_LIBRARY_PATH", "")
-    return os.path.join(cpp, "_build", name), env
 
 
 # ---- admission
